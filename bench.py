@@ -17,7 +17,13 @@ longest-processing-time on the fit cost N K^2 + 8 N P; there is no data-path col
 The step includes the noise realisations GLSFitter.fit_toas computes when full_cov=False
 (fitter.py:2269-2282): k_noise_red after the solve, the per-pulsar arrays copied to the host.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+every other leg: the Gram kernel's event timing and the roofline record, the weak-scaling
+PTA (N > 1), the cold start, the predicted strong scaling, the chi2 grids, the J0740 and
+B1855 legs and the CPU baseline (each with its own switch, as before).  --dump-outputs DIR
+writes what the last timed step handed to its caller (DIR/<name>.npy).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -66,6 +72,11 @@ def main():
     ap.add_argument("--max-pipes", type=int, default=2)
     ap.add_argument("--cold-start", type=int, default=1,
                     help="N=1 only: upload + first fit of the PTA in a fresh session (cold_start)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: Gram event timing and roofline, weak scaling, "
+                         "cold start, predicted strong scaling, grids, J0740, C2, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fit outputs of the last timed step (rank 0's shard) as DIR/<name>.npy")
     args = ap.parse_args()
 
     # (several pipelines share the process's GPU_MAX_HW_QUEUES hardware queues, default 4:
@@ -114,10 +125,11 @@ def main():
     models = [sim.pta_model(i) for i in range(args.npsr)]
     costs = [fit_cost(m, n=args.ntoas) for m in models]
     shards = lpt_shard(costs, world)
-    leg = pta_leg(shards[rank], models, args, rank, barrier, max_over_ranks, profile=True)
+    leg = pta_leg(shards[rank], models, args, rank, barrier, max_over_ranks, profile=args.full,
+                  dump=args.dump_outputs if rank == 0 else None)
     fits_per_s = args.npsr / (leg["dt"] / args.steps)
     weak = None
-    if world > 1 and args.weak:
+    if args.full and world > 1 and args.weak:
         # extra: weak scaling, a 68 x N pulsar PTA (pulsar i uses seed i), ~68 per rank
         ntot = args.npsr * world
         models_w = models + [sim.pta_model(i) for i in range(args.npsr, ntot)]
@@ -129,18 +141,18 @@ def main():
                 "ms_per_step": round(leg2["dt"] / args.steps * 1e3, 4),
                 "pulsars_per_rank": [len(s) for s in sh2]}
 
-    roof = leg["roofline"]
-    cold = cold_start(leg["items"], rank) if (world == 1 and args.cold_start) else None
-    emu = None
-    if world == 1 and args.emulate_world:
-        emu = emulate_world(leg["items"], costs, [int(x) for x in args.emulate_world.split(",") if x],
-                            args, fits_per_s, leg["dt"] / args.steps)
-    grid = grid_leg(args.grid, dist, barrier, max_over_ranks) if args.grid > 0 else None
-    j0740 = j0740_legs(args.j0740, dist, barrier, max_over_ranks) if args.j0740 > 0 else None
-    c2 = c2_leg(args.c2, 20, 3, world, barrier, max_over_ranks, npipes(args)) if args.c2 > 0 else None
-    cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline:
-        cpu = cpu_baseline(leg["items"])
+    roof = leg.get("roofline")
+    cold = emu = grid = j0740 = c2 = cpu = None
+    if args.full:
+        cold = cold_start(leg["items"], rank) if (world == 1 and args.cold_start) else None
+        if world == 1 and args.emulate_world:
+            emu = emulate_world(leg["items"], costs, [int(x) for x in args.emulate_world.split(",") if x],
+                                args, fits_per_s, leg["dt"] / args.steps)
+        grid = grid_leg(args.grid, dist, barrier, max_over_ranks) if args.grid > 0 else None
+        j0740 = j0740_legs(args.j0740, dist, barrier, max_over_ranks) if args.j0740 > 0 else None
+        c2 = c2_leg(args.c2, 20, 3, world, barrier, max_over_ranks, npipes(args)) if args.c2 > 0 else None
+        if rank == 0 and world == 1 and args.cpu_baseline:
+            cpu = cpu_baseline(leg["items"])
 
     if rank == 0:
         out = {"metric": "GLS fits/sec, 68-PSR x 10k-TOA synthetic PTA (whole node)", "value": round(fits_per_s, 3),
@@ -156,23 +168,26 @@ def main():
                           "parallelism": f"pulsar shards x{world} (LPT, no data-path collective)"},
                "roofline": roof, "pta_weak": weak, "predicted_strong": emu, "cold_start": cold,
                "grid": grid, "j0740": j0740, "c2": c2,
-               "cpu_baseline": cpu}
+               "cpu_baseline": cpu, "full": bool(args.full)}
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
 
 
-def pta_leg(mine, models, args, rank, barrier, max_over_ranks, profile):
+def pta_leg(mine, models, args, rank, barrier, max_over_ranks, profile, dump=None):
     """Time K steps (GLSFitter maxiter=1 of every pulsar in `mine`) on this rank's GPU;
-    returns the max-over-ranks wall time and, with profile, the roofline record."""
+    returns the max-over-ranks wall time and, with profile, the roofline record (the Gram
+    kernel's event pass and the instrumented steps run only then).  dump: a directory for
+    the last timed step's outputs (dump_outputs)."""
     from pint_amd import simulation as sim
     from pint_amd.engine import Session, build_layout, pack_table
     t0 = time.time()
     items = sim.make_pta(ntoas=args.ntoas, indices=mine, models=[models[i] for i in mine])
     log(f"[rank {rank}] generated {len(items)} pulsars x {args.ntoas} TOAs in {time.time() - t0:.1f}s")
     ss, lays = pipelines(items, npipes(args))
-    dt, kt_gram, n_gram, step, launch, p = timed_steps(ss, args.steps, args.warmup, barrier, max_over_ranks,
-                                                       graph=args.graph, pipes=args.pipes)
+    dt, kt_gram, n_gram, step, launch, p = timed_steps(
+        ss, args.steps, args.warmup, barrier, max_over_ranks, graph=args.graph, gram_pass=profile, pipes=args.pipes,
+        on_timed=(lambda s, outs: dump_outputs(dump, s, outs)) if dump else None)
     out = {"dt": dt, "items": items, "kmax": int(max(l.K for l in lays)), "launch": launch, "pipes": p}
     if profile:
         out["roofline"] = roofline(ss[0], lays, kt_gram / max(1, n_gram), step, args)
@@ -180,6 +195,39 @@ def pta_leg(mine, models, args, rank, barrier, max_over_ranks, profile):
     for s in ss:
         s.close()
     return out
+
+
+DUMP_MAX_BYTES = 60 << 20  # all of a dump's arrays together (float64)
+
+
+def dump_outputs(path, s, outs):
+    """Write what the last timed step handed to its caller as path/<name>.npy (float64, the
+    instances of session `s` concatenated in batch order): steps, errors (K+1 per instance),
+    covariances (the timing covariance matrices, flattened), chi2_linearised and chi2 (one per
+    instance), and the noise realisations per component (n per instance that has it).  Arrays
+    that together would pass DUMP_MAX_BYTES are cut to a fixed, seeded sample of their
+    elements (the same indices for the same arguments)."""
+    (st, er, covs, cl), nz, c2 = outs
+    arrs = {"steps": st.flat, "errors": er.flat, "covariances": covs.flat, "chi2_linearised": cl, "chi2": c2}
+    if nz is not None:
+        per = [nz[k] for k in range(len(nz))]
+        for name in ("pl_red_noise", "ecorr_noise", "pl_DM_noise"):
+            parts = [d[name] for d in per if name in d]
+            if parts:
+                arrs[name] = np.concatenate(parts)
+    arrs = {k: np.array(v, dtype=np.float64).ravel() for k, v in arrs.items()}
+    # the budget shared evenly; what a small array leaves goes to the larger ones
+    left, todo = DUMP_MAX_BYTES // 8, sorted(arrs, key=lambda k: arrs[k].size)
+    for i, k in enumerate(todo):
+        share = left // (len(todo) - i)
+        if arrs[k].size > share:
+            idx = np.sort(np.random.default_rng(0).choice(arrs[k].size, size=share, replace=False))
+            arrs[k] = arrs[k][idx]
+        left -= arrs[k].size
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    log(f"[dump] {', '.join(f'{k} {v.size}' for k, v in arrs.items())} -> {path}")
 
 
 def npipes(args):
@@ -283,7 +331,8 @@ def cold_start(items, rank):
     return out
 
 
-def timed_steps(sessions, steps, warmup, barrier, max_over_ranks, graph="auto", gram_pass=True, pipes=1):
+def timed_steps(sessions, steps, warmup, barrier, max_over_ranks, graph="auto", gram_pass=True, pipes=1,
+                on_timed=None):
     """Time `steps` fit steps of the batch (warm-up first); one step is
     GLSFitter.fit_toas(maxiter=1) of every instance from its initial model.
 
@@ -296,6 +345,9 @@ def timed_steps(sessions, steps, warmup, barrier, max_over_ranks, graph="auto", 
     graph: 0 enqueue every launch of every step from the host; 1 capture the step once per
     pipeline slot into a HIP graph and replay it (the same kernels, copies and outputs, one
     host launch per step); "auto" the faster of the two on the trial.
+    on_timed(session, outputs): called once the timed steps have ended, before any later
+    pass reuses the buffers, with the session of the last timed step and what that step
+    handed out: ((steps, errors, covariances, linearised chi2), noise views, chi2).
     Returns (max-over-ranks seconds, summed Gram event time of the sampled steps, their
     count, step, launch mode, pipelines)."""
     from collections import deque
@@ -328,11 +380,15 @@ def timed_steps(sessions, steps, warmup, barrier, max_over_ranks, graph="auto", 
     def step(s):
         """The same step enqueued by one call (pint_fit_step_enqueue, closes the step);
         returns its slot."""
-        return s.fit_step_enqueue(restore=True, lam=1.0)[0]
+        r = s.fit_step_enqueue(restore=True, lam=1.0)
+        outs[id(s), r[0]] = r[1:]
+        return r[0]
 
     def replay(s):
         s.replay()
         return s.step_end()
+
+    outs = {}  # (session, slot) -> the outputs handed out by the last step enqueued there
 
     def run(nsteps, launch, sess):
         """nsteps steps over the pipelines `sess`, round-robin, each pipelined L.NSLOT deep:
@@ -360,9 +416,13 @@ def timed_steps(sessions, steps, warmup, barrier, max_over_ranks, graph="auto", 
                 check_one(k)
             if tr is not None:
                 tr[2 * i] = clk()
-            pend[k].append(launch(sess[k]))
+            sl = launch(sess[k])
+            pend[k].append(sl)
             if tr is not None:
                 tr[2 * i + 1] = clk()
+        if nsteps > 0:
+            outs["last"] = outs.get((id(sess[k]), sl))
+            outs["last_session"] = sess[k]
         for k in range(len(sess)):
             while pend[k]:
                 check_one(k)
@@ -389,21 +449,24 @@ def timed_steps(sessions, steps, warmup, barrier, max_over_ranks, graph="auto", 
     gc.disable()
     try:
         return _timed(sessions, steps, warmup, barrier, max_over_ranks, graph, gram_pass, pipes, run, step,
-                      step_calls, replay)
+                      step_calls, replay, outs, on_timed)
     finally:
         gc.enable()
         gc.unfreeze()
 
 
-def _timed(sessions, steps, warmup, barrier, max_over_ranks, graph, gram_pass, pipes, run, step, step_calls, replay):
+def _timed(sessions, steps, warmup, barrier, max_over_ranks, graph, gram_pass, pipes, run, step, step_calls, replay,
+           outs, on_timed):
     from pint_amd import _lib as L
     run(warmup * len(sessions), step, sessions)  # every pipeline warmed up
     if graph in (1, "1", "auto"):
         for s in sessions:
             s.set_timing_mask(0)
             for _ in range(L.NSLOT):  # one graph per pipeline slot
-                s.capture(lambda: step_calls(s))
-                s.check_step(s.step_end())
+                o = s.capture(lambda: step_calls(s))
+                sl = s.step_end()
+                outs[id(s), sl] = o  # (pinned buffers that every replay of this slot's graph refills)
+                s.check_step(sl)
     # the candidates (launch mode, pipelines): fixed by the arguments, or timed on a short
     # trial each and the fastest kept
     modes = {"0": ["direct"], "1": ["hip-graph"], "auto": ["direct", "hip-graph"]}[str(graph)]
@@ -427,6 +490,8 @@ def _timed(sessions, steps, warmup, barrier, max_over_ranks, graph, gram_pass, p
     run(steps, replay if mode == "hip-graph" else step, sessions[:p])
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    if on_timed is not None and outs.get("last") is not None:
+        on_timed(outs["last_session"], outs["last"])
     # the Gram kernel's time: the same step with its events, after the timed region
     kt, nk = 0.0, 0
     s0 = sessions[0]

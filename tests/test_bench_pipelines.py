@@ -104,3 +104,42 @@ def test_trial_keeps_the_fastest_candidate(bench_mod, monkeypatch):
     _, _, _, _, mode, p = bench.timed_steps(ss, 40, 2, lambda: None, lambda v: v, graph="0", gram_pass=False,
                                             pipes="auto")
     assert (mode, p) == ("direct", 2)
+
+
+def test_on_timed_gets_the_last_timed_step(bench_mod):
+    """The hook runs once, after the timed steps, with the session of the last timed step
+    (step 20 of 21 over two pipelines: the first) and what that step handed out."""
+    bench, nslot = bench_mod
+    ss = [FakeSession("a", nslot), FakeSession("b", nslot)]
+    seen = []
+    bench.timed_steps(ss, 21, 3, lambda: None, lambda v: v, graph="0", gram_pass=False, pipes=2,
+                      on_timed=lambda s, outs: seen.append((s.name, outs, s.enqueued, s.retired)))
+    assert len(seen) == 1
+    name, outs, enq, ret = seen[0]
+    assert name == "a" and outs == (None, None, None)
+    assert enq == ret  # every step retired before the outputs are read
+
+
+def test_dump_outputs_files_and_seeded_sample(bench_mod, tmp_path, monkeypatch):
+    import numpy as np
+    from pint_amd.engine import SplitView
+    bench, _ = bench_mod
+    rng = np.random.default_rng(1)
+    offk, offc = np.array([0, 3, 8]), np.array([0, 4, 20])
+    dp, er, cov = rng.normal(size=8), rng.normal(size=8), rng.normal(size=20)
+    cl, c2 = rng.normal(size=2), rng.normal(size=2)
+    outs = ((SplitView(dp, offk), SplitView(er, offk), SplitView(cov, offc, [(2, 2), (4, 4)]), cl), None, c2)
+    bench.dump_outputs(str(tmp_path / "d"), None, outs)
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in sorted(os.listdir(tmp_path / "d"))}
+    assert sorted(got) == ["chi2", "chi2_linearised", "covariances", "errors", "steps"]
+    for k, ref in (("steps", dp), ("errors", er), ("covariances", cov), ("chi2_linearised", cl), ("chi2", c2)):
+        assert got[k].dtype == np.float64 and np.array_equal(got[k], ref)
+    # over the budget: every array cut to the same seeded sample on every call, within it
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 20)
+    for d in ("e", "f"):
+        bench.dump_outputs(str(tmp_path / d), None, outs)
+    e = {f: np.load(tmp_path / "e" / f) for f in os.listdir(tmp_path / "e")}
+    f = {f: np.load(tmp_path / "f" / f) for f in os.listdir(tmp_path / "f")}
+    assert sum(v.nbytes for v in e.values()) <= 8 * 20
+    assert all(np.array_equal(e[k], f[k]) for k in e)
+    assert np.array_equal(e["chi2.npy"], c2) and set(e["covariances.npy"]) <= set(cov)
