@@ -101,7 +101,9 @@ enum {
     PINT_COL_OFFSET = 0, PINT_COL_F = 1, PINT_COL_LON = 2, PINT_COL_LAT = 3,
     PINT_COL_PMLON = 4, PINT_COL_PMLAT = 5, PINT_COL_PX = 6, PINT_COL_DM = 7,
     PINT_COL_DMX = 8, PINT_COL_FD = 9, PINT_COL_JUMP = 10, PINT_COL_BIN = 11,
-    PINT_COL_ZERO = 12      /* a parameter without a delay (DMJUMP, dispersion_model.py:797) */
+    PINT_COL_ZERO = 12,     /* a parameter without a delay (DMJUMP, dispersion_model.py:797) */
+    PINT_COL_NESW = 13      /* NE_SW: d_delay_d_ne_sw = DMconst * solar_wind_geometry / bfreq^2
+                               (solar_wind_dispersion.py:404-412), d_dm_d_ne_sw = the geometry (:394) */
 };
 /* binary parameter ids (stand_alone_psr_binaries/binary_generic.py, ELL1_model.py, DD_model.py,
  * ELL1H_model.py (H3, H4, STIGMA), DDK_model.py (KIN, KOM)) */
@@ -154,7 +156,14 @@ typedef struct {
     int32_t ndmjump;        /* DMJUMPs (<= 64; bit k of the per-TOA DMJUMP mask selects DMJUMP k+1) */
     double obliquity;       /* rad, ecliptic models (pulsar_ecliptic.py OBL[ECL])       */
     double red_f0;          /* red-noise fundamental 1/T (Hz), noise_model.py:847       */
-    double red_t0;          /* unused reserve                                           */
+    int32_t o_NE_SW;        /* SolarWindDispersion, SWM 0: table slot of NE_SW (cm^-3; -1 absent, or
+                               present, zero and frozen: the reference's delay is then zeros,
+                               solar_wind_dispersion.py:388-392).  DM_sw = NE_SW * AU^2 rho /
+                               (r sin rho) in pc, rho = pi - the pulsar-observatory-Sun angle
+                               (:356-360, astrometry.py:114-150; Edwards et al. 2006 eq. 29-30);
+                               its delay joins the sum after the Solar-system Shapiro delay and
+                               before DispersionDM (timing_model.py DEFAULT_ORDER)              */
+    int32_t rsv_;           /* unused reserve (keeps the header a whole number of doubles)      */
     int32_t col_kind[PINT_MAX_COLS];
     int32_t col_index[PINT_MAX_COLS];
     int32_t col_toff[PINT_MAX_COLS];  /* table offset of the column's parameter (-1: Offset) */

@@ -409,6 +409,20 @@ PD void psr_dir_icrs(const InstConst& C, double epoch_mjd, double L[3]) {
     }
 }
 
+// SolarWindDispersion.solar_wind_geometry for SWM 0 (solar_wind_dispersion.py:356-360; Edwards
+// et al. 2006 eq. 29-30) in pc: AU^2 rho / (r sin rho), rho = pi - theta, with theta the angle at
+// the observatory between the Sun (sun = obs_sun_pos, km; r its length) and the pulsar direction
+// L, cos theta = (sun / r) . L and theta = arccos of it as in sun_angle (astrometry.py:146-150).
+// DM_sw = NE_SW * this; d_dm_d_ne_sw is this (:394-402).  The one formula of the evaluation
+// (k_sw_geom forms it per row, eval_pre reads it) and of the wideband DM rows (k_dm_resid, wb_row).
+PD double solar_wind_geometry_pc(const double sun[3], const double L[3]) {
+    const double r = sqrt(sun[0] * sun[0] + sun[1] * sun[1] + sun[2] * sun[2]);
+    const double ir = 1.0 / r;
+    const double ct = (sun[0] * ir) * L[0] + (sun[1] * ir) * L[1] + (sun[2] * ir) * L[2];
+    const double rho = PI_D - acos(ct);
+    return (AU_KM * AU_KM * (1000.0 * INV_KPC_KM)) * rho / (r * sin(rho));
+}
+
 // ------------------------------------------------------------------------------------
 // Binary models.  Base quantities are computed once per TOA; d_delay/d(param) per column.
 // All derivatives are per SI unit of the parameter (s, rad, rad/s, ...), converted to the
@@ -1104,8 +1118,9 @@ struct EvalHead {
     double delay;                          // total delay (s)
     double gLON, gLAT, gPMLON, gPMLAT, gPX;  // astrometric geometry without the chain factor
     double inv_f2, dt_yr_dm, logf;
+    double swg;  // solar-wind geometry (pc) without the chain factor; 0 without NE_SW
 };
-constexpr int EVAL_HEAD_W = 9;  // doubles of an EvalHead row
+constexpr int EVAL_HEAD_W = 10;  // doubles of an EvalHead row
 
 // eval_toa after the delay: the spin frequency at dt (dt0 - delay) and at dt0, the chain
 // factor of the design matrix
@@ -1129,7 +1144,7 @@ PD void eval_spin_a(const pint_spec_t& S, const double* P, const InstConst& C, c
 template <int BIN>
 PD void eval_spin_b(const pint_spec_t& S, const double* P, const InstConst& C, const ToaRow& t, const EvalHead& h,
                     const EvalSpin& sp, EvalOut& o, double* Mb, unsigned r, long ld, const ColRun* runs, int nrun,
-                    bool compact) {
+                    bool compact, const double* swg = nullptr) {
     const double chain = sp.chain, dtd = sp.dtd;
     // ---- spindown phase (spindown.py:124-155) + jumps (jump.py:119-136) ----
     dd ph = spin_phase(S, P, sp.dt);
@@ -1184,6 +1199,18 @@ PD void eval_spin_b(const pint_spec_t& S, const double* P, const InstConst& C, c
                     colp[r] = dmc * v;
                 }
             } break;
+            case PINT_COL_NESW: {  // d_delay_d_ne_sw (solar_wind_dispersion.py:404-412): 0 below 1 MHz
+                // the geometry from the shared head (k_eval_spin), else read again here, through a
+                // row index the compiler cannot see through: merged with eval_pre's load the value
+                // would stay in registers across the binary state
+                double g = h.swg;
+                if (swg) {
+                    unsigned rr = r;
+                    asm volatile("" : "+v"(rr));
+                    g = swg[rr];
+                }
+                colp[r] = h.inv_f2 > 1.0 ? 0.0 : dmc * g;
+            } break;
             case PINT_COL_DMX:  // d_dm_d_DMX (:684): 1 on the bin's TOAs
                 for (int j = 0; j < R.cnt; j++, colp += ld) {
                     const int idx = R.idx0 + j;
@@ -1219,7 +1246,7 @@ struct EvalPre {
     double L[3];
 };
 PD void eval_pre(const pint_spec_t& S, const double* P, const InstConst& C, const ToaRow& t, EvalOut& o, bool wantM,
-                 EvalPre& pre) {
+                 EvalPre& pre, const double* swg, unsigned r) {
     o.status = 0;
     o.dmc = 0.0;
     double delay = 0.0;
@@ -1268,6 +1295,12 @@ PD void eval_pre(const pint_spec_t& S, const double* P, const InstConst& C, cons
     }
     double inv_f2 = 1.0 / (bfreq * bfreq);
     o.inv_f2 = inv_f2;
+    // ---- SolarWindDispersion, SWM 0 (solar_wind_dispersion.py:370-392): after the Shapiro delay
+    //      and before DispersionDM in the sum (DEFAULT_ORDER); no barycentre skip.  The geometry
+    //      (an acos, a sin, a sqrt and two divisions per TOA) is read, not formed here: inside the
+    //      evaluation its temporaries spilled the builds that run at a fixed register budget.
+    //      Uniform per instance. ----
+    if (S.o_NE_SW >= 0) delay += (pval(P, S.o_NE_SW) * swg[r]) * DMCONST * inv_f2;
     // ---- DispersionDM (dispersion_model.py:217-234) ----
     double dt_yr_dm = 0.0;
     if (S.ndm > 0) {
@@ -1331,7 +1364,7 @@ PD void eval_pre(const pint_spec_t& S, const double* P, const InstConst& C, cons
         // d_delay_astrometry_d_PX (astrometry.py:219-249)
         gPX = 0.5 * ((rr - re_dot_L * re_dot_L) * INV_AUC) * MAS_RAD;
     }
-    pre.h = {delay, gLON, gLAT, gPMLON, gPMLAT, gPX, inv_f2, dt_yr_dm, logf};
+    pre.h = {delay, gLON, gLAT, gPMLON, gPMLAT, gPX, inv_f2, dt_yr_dm, logf, 0.0};
     pre.fd = fd;
     pre.L[0] = L[0];
     pre.L[1] = L[1];
@@ -1339,19 +1372,23 @@ PD void eval_pre(const pint_spec_t& S, const double* P, const InstConst& C, cons
 }
 
 // the shared head of a spin-only grid (k_eval_head): eval_toa's operations up to the spin part
-PD void eval_head(const pint_spec_t& S, const double* P, const InstConst& C, const ToaRow& t, EvalHead& h) {
+PD void eval_head(const pint_spec_t& S, const double* P, const InstConst& C, const ToaRow& t, EvalHead& h,
+                  const double* swg, unsigned r) {
     EvalOut o;
     EvalPre pre;
-    eval_pre(S, P, C, t, o, true, pre);
+    eval_pre(S, P, C, t, o, true, pre, swg, r);
     h = pre.h;
+    if (S.o_NE_SW >= 0) h.swg = swg[r];
     if (S.nfd > 0) h.delay += pre.fd;
 }
 
 template <int BIN>
 PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, const ToaRow& t, EvalOut& o,
-                 double* Mb, unsigned r, long ld, const ColRun* runs, int nrun, bool compact) {
+                 double* Mb, unsigned r, long ld, const ColRun* runs, int nrun, bool compact, const double* swg) {
+    // swg: the instance's rows of solar-wind geometry (pc; solar_wind_geometry_pc, formed before the
+    // evaluation), read when the model has NE_SW
     EvalPre pre;
-    eval_pre(S, P, C, t, o, Mb != nullptr, pre);
+    eval_pre(S, P, C, t, o, Mb != nullptr, pre, swg, r);
     double delay = pre.h.delay;
     const double* L = pre.L;
     const double fd = pre.fd;
@@ -1406,8 +1443,8 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
             }
         }
     }
-    const EvalHead h = {delay, gLON, gLAT, gPMLON, gPMLAT, gPX, inv_f2, dt_yr_dm, logf};
-    eval_spin_b<BIN>(S, P, C, t, h, sp, o, Mb, r, ld, runs, nrun, compact);
+    const EvalHead h = {delay, gLON, gLAT, gPMLON, gPMLAT, gPX, inv_f2, dt_yr_dm, logf, 0.0};
+    eval_spin_b<BIN>(S, P, C, t, h, sp, o, Mb, r, ld, runs, nrun, compact, S.o_NE_SW >= 0 ? swg : nullptr);
 }
 
 }  // namespace pint

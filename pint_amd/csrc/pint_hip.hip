@@ -429,6 +429,7 @@ struct EvalRestore {
     InstConst* ic;
     double* rph;    // fused residual pass (null: k_resid1 follows): phase residuals (output rows)
     double* epart;  // ... and the blocks' (sum w, sum w x) partials
+    const double* swg;  // the evaluation rows' solar-wind geometry (k_sw_geom); null: no instance has NE_SW
 };
 
 // the TOA inputs of row r (row n: the TZR TOA)
@@ -459,14 +460,14 @@ __device__ __forceinline__ void eval_row(const pint_spec_t& S, EvalLds& L, const
                                          int write_red, int* __restrict__ status, int* __restrict__ istatus, int ii,
                                          double* __restrict__ ph_hi, double* __restrict__ ph_lo,
                                          double* __restrict__ ftay, double* __restrict__ delay_out,
-                                         double* __restrict__ dfac, EvalOut& o) {
+                                         double* __restrict__ dfac, const double* __restrict__ swg, EvalOut& o) {
     const double* P = stP ? L.P : tables + I.toff;
     ToaRow t;
     load_toa_row(Pd, S, r, t);
     double* Mb = WANT_M ? (Mout + I.moff) : nullptr;  // wave-uniform column base
     const bool rowM = WANT_M && own && r < (unsigned)n;
     const bool cmp = WANT_M && compact && Pd.dsplit;
-    eval_toa<BIN>(S, P, L.C, t, o, rowM ? Mb : nullptr, r, n, stR ? L.R : Pd.runs, nrun, cmp);
+    eval_toa<BIN>(S, P, L.C, t, o, rowM ? Mb : nullptr, r, n, stR ? L.R : Pd.runs, nrun, cmp, swg ? swg + I.roff : nullptr);
     if (!own) return;
     if (rowM && cmp) dmxv[I.ooff + r] = o.dmc;
     if (o.status) {  // the batch's status word and this instance's own (pint_inst_status)
@@ -574,7 +575,7 @@ __device__ __forceinline__ void eval_block(int b, const PsrDev* __restrict__ psr
     }
     EvalOut o;
     eval_row<WANT_M, BIN>(S, L, Pd, I, stP, stR, nrun, tables, r, n, own, Mout, dmxv, compact, write_red, status, istatus,
-                          ii, ph_hi, ph_lo, ftay, delay_out, dfac, o);
+                          ii, ph_hi, ph_lo, ftay, delay_out, dfac, rs.swg, o);
     wgp_stamp(1, false);
     if (!ef) return;
     // ---- the fused k_resid1 (residuals.py:314-425): tz and d0 from the block's own TZR and
@@ -617,6 +618,29 @@ __device__ __forceinline__ void eval_block(int b, const PsrDev* __restrict__ psr
     }
 }
 
+// k_sw_geom: the solar-wind geometry (solar_wind_geometry_pc, pc) of every evaluation row (TOAs
+// and the TZR row) of the instances whose model has NE_SW, before the evaluation that reads it
+// (eval_pre's delay term, the NE_SW design-matrix column).  It depends on the TOA's Sun vector
+// and the pulsar direction (the per-instance constants) only.  A pass of its own: formed inside
+// k_eval, the acos / sin temporaries raised the register count of every build, spilling the
+// ones at a fixed budget.  Grid (instances, row blocks of the longest instance); ~40 B/row.
+// (row i of a pulsar: a TOA or the TZR row; the pulsar direction at its epoch as eval_pre forms it)
+__device__ __forceinline__ double sw_geometry_row(const PsrDev& Pd, const InstConst& C, int i) {
+    double L[3];
+    psr_dir_icrs(C, dd_to_d(dd_make(Pd.tdb_hi[i], Pd.tdb_lo[i])), L);
+    const double sun[3] = {Pd.sun[3 * i], Pd.sun[3 * i + 1], Pd.sun[3 * i + 2]};
+    return solar_wind_geometry_pc(sun, L);
+}
+__global__ __launch_bounds__(256) void k_sw_geom(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
+                                                 const InstConst* __restrict__ ic, double* __restrict__ swg) {
+    const InstDev I = insts[blockIdx.x];
+    const PsrDev& Pd = psrs[I.psr];
+    if (Pd.spec->o_NE_SW < 0) return;  // (block-uniform)
+    const int r = blockIdx.y * 256 + threadIdx.x;
+    if (r > I.n) return;
+    swg[I.roff + r] = sw_geometry_row(Pd, ic[blockIdx.x], r);
+}
+
 // Spin-only grids (pint_set_grid's variables all spin frequencies, isolated model, no
 // red-noise basis, the full layout): before the first fit step every point shares its
 // delays, astrometric geometry and dispersion factors (they depend on the TOAs and the
@@ -627,7 +651,7 @@ __device__ __forceinline__ void eval_block(int b, const PsrDev* __restrict__ psr
 // each point: the same bits (test_spin_grid_eval_matches_full).
 __global__ __launch_bounds__(256) void k_eval_head(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
                                                    const double* __restrict__ tables, const InstConst* __restrict__ ic,
-                                                   double* __restrict__ shr) {
+                                                   const double* __restrict__ swg, double* __restrict__ shr) {
     const InstDev I = insts[0];
     const PsrDev& Pd = psrs[I.psr];
     const pint_spec_t& S = *Pd.spec;
@@ -636,7 +660,7 @@ __global__ __launch_bounds__(256) void k_eval_head(const PsrDev* __restrict__ ps
     ToaRow t;
     load_toa_row(Pd, S, r, t);
     EvalHead h;
-    eval_head(S, tables + I.toff, ic[0], t, h);
+    eval_head(S, tables + I.toff, ic[0], t, h, swg ? swg + I.roff : nullptr, r);
     double* o = shr + (long)r * EVAL_HEAD_W;
     o[0] = h.delay;
     o[1] = h.gLON;
@@ -647,6 +671,7 @@ __global__ __launch_bounds__(256) void k_eval_head(const PsrDev* __restrict__ ps
     o[6] = h.inv_f2;
     o[7] = h.dt_yr_dm;
     o[8] = h.logf;
+    o[9] = h.swg;
 }
 
 // a wave per point, lanes over its rows
@@ -675,7 +700,7 @@ __global__ __launch_bounds__(256) void k_eval_spin(const PsrDev* __restrict__ ps
         t.dmx_x0 = Pd.dmx_x ? Pd.dmx_x[r] : 0;
         t.dmx_x1 = Pd.dmx_x ? Pd.dmx_x[r + 1] : 0;
         const double* q = shr + (long)r * EVAL_HEAD_W;
-        const EvalHead h = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]};
+        const EvalHead h = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9]};
         EvalOut o;
         o.status = 0;
         o.dmc = 0.0;
@@ -2203,12 +2228,14 @@ __global__ __launch_bounds__(GW * 64, GWG) void k_gram_v(const PsrDev* __restric
 // k_dm_resid: WidebandDMResiduals (residuals.py:1000-1031) of an instance, one workgroup per
 // instance: the modelled DM (timing_model.py:1593 total_dm: DispersionDM.base_dm, a Taylor
 // series in Julian years from DMEPOCH, dispersion_model.py:217-234; DispersionDMX.dmx_dm
-// :659-678; DispersionJump.jump_dm, -DMJUMP on its TOAs :773-785) at the instance's
+// :659-678; DispersionJump.jump_dm, -DMJUMP on its TOAs :773-785; SolarWindDispersion.
+// solar_wind_dm, NE_SW times the SWM 0 geometry, solar_wind_dispersion.py:370-386) at the instance's
 // parameters, r = pp_dm - DM; the mean (weights 1/pp_dme^2, unscaled) removed if asked; chi2
 // with the scaled errors.  Sums in a fixed order (deterministic).  Bandwidth: ~48 B/TOA.
 constexpr int DMR_T = 256;
 __global__ __launch_bounds__(DMR_T) void k_dm_resid(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
-                                                    const double* __restrict__ tables, int subtract_mean,
+                                                    const double* __restrict__ tables,
+                                                    const InstConst* __restrict__ ic, int subtract_mean,
                                                     int use_weighted_mean, double* __restrict__ rout,
                                                     double* __restrict__ chi2) {
     __shared__ double sh[DMR_T / 64];
@@ -2246,6 +2273,7 @@ __global__ __launch_bounds__(DMR_T) void k_dm_resid(const PsrDev* __restrict__ p
             for (int k = 0; k < S.ndmjump; k++)
                 if ((m >> k) & 1ull) dm -= pval(P, S.o_DMJUMP + 2 * k);
         }
+        if (S.o_NE_SW >= 0) dm += pval(P, S.o_NE_SW) * sw_geometry_row(Pd, ic[blockIdx.x], i);  // solar_wind_dm
         const double v = Pd.pp_dm[i] - dm;
         r[i] = v;
         if (subtract_mean) {
@@ -2280,9 +2308,9 @@ __global__ __launch_bounds__(DMR_T) void k_dm_resid(const PsrDev* __restrict__ p
 // sums of squares (the normalisation, utils.py:2879), and per DMX bin DD += sum w, DCS +=
 // count, Sd[.][c] += sum w d_c, Sd[.][res] += sum w r (the bin stays diagonal).  Compact
 // layout only (the host checks).  One workgroup per instance; sums in a fixed order.
-constexpr int WB_MAXC = 8;  // dense DM-type columns (DM Taylor terms + DMJUMPs)
-__device__ __forceinline__ void wb_row(const PsrDev& Pd, const pint_spec_t& S, const double* P, int i, bool any,
-                                       dd ep, double& r, double& w, double& dtyr) {
+constexpr int WB_MAXC = 8;  // dense DM-type columns (DM Taylor terms + DMJUMPs + NE_SW, whose entry is the geometry)
+__device__ __forceinline__ void wb_row(const PsrDev& Pd, const pint_spec_t& S, const double* P, const InstConst& C,
+                                       int i, bool any, dd ep, double& r, double& w, double& dtyr, double& swg) {
     double dm = 0.0;
     dtyr = S.o_DMEPOCH >= 0 ? dd_to_d(dd_sub(dd_make(Pd.tdb_hi[i], Pd.tdb_lo[i]), ep)) * INV_DJY : 0.0;
     if (S.ndm > 0) {
@@ -2302,20 +2330,27 @@ __device__ __forceinline__ void wb_row(const PsrDev& Pd, const pint_spec_t& S, c
         for (int k = 0; k < S.ndmjump; k++)
             if ((m >> k) & 1ull) dm -= pval(P, S.o_DMJUMP + 2 * k);
     }
+    swg = 0.0;
+    if (S.o_NE_SW >= 0) {  // solar_wind_dm (solar_wind_dispersion.py:370-386)
+        swg = sw_geometry_row(Pd, C, i);
+        dm += pval(P, S.o_NE_SW) * swg;
+    }
     r = Pd.pp_dm[i] - dm;
     const double is = 1.0 / Pd.dm_sig[i];
     w = is * is;
 }
-__device__ __forceinline__ double wb_deriv(const PsrDev& Pd, int kind, int idx, int i, double dtyr) {
+__device__ __forceinline__ double wb_deriv(const PsrDev& Pd, int kind, int idx, int i, double dtyr, double swg) {
     if (kind == PINT_COL_DM) {  // d_dm_d_DMs (dispersion_model.py:253-275)
         double v = 1.0;
         for (int j = 1; j <= idx; j++) v = v * dtyr * inv_int(j);
         return v;
     }
+    if (kind == PINT_COL_NESW) return swg;  // d_dm_d_ne_sw (solar_wind_dispersion.py:394-402)
     return ((Pd.dmjmask[i] >> idx) & 1ull) ? -1.0 : 0.0;  // DMJUMP (:787-795)
 }
 __global__ __launch_bounds__(256) void k_wb_gram(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
-                                                 const double* __restrict__ tables, int nsplit,
+                                                 const double* __restrict__ tables,
+                                                 const InstConst* __restrict__ ic, int nsplit,
                                                  double* __restrict__ Gpart, double* __restrict__ colsq,
                                                  double* __restrict__ Sd, double* __restrict__ DD,
                                                  double* __restrict__ DCS) {
@@ -2325,12 +2360,13 @@ __global__ __launch_bounds__(256) void k_wb_gram(const PsrDev* __restrict__ psrs
     if (!Pd.wb || !Pd.dsplit) return;
     const pint_spec_t& S = *Pd.spec;
     const double* P = tables + I.toff;
+    const InstConst& C = ic[blockIdx.x];
     const int n = I.n, Kp = Pd.Kpd, Kres = Pd.Kd;
     // the dense DM-type columns (compact index, kind, index)
     int cc[WB_MAXC], kd[WB_MAXC], ix[WB_MAXC], m = 0;
     for (int c = 0; c < S.ncol && m < WB_MAXC; c++) {
         const int k = S.col_kind[c];
-        if ((k == PINT_COL_DM || k == PINT_COL_ZERO) && Pd.cmap[c] >= 0) {
+        if ((k == PINT_COL_DM || k == PINT_COL_ZERO || k == PINT_COL_NESW) && Pd.cmap[c] >= 0) {
             cc[m] = Pd.cmap[c];
             kd[m] = k;
             ix[m] = S.col_index[c];
@@ -2347,11 +2383,11 @@ __global__ __launch_bounds__(256) void k_wb_gram(const PsrDev* __restrict__ psrs
 #pragma unroll
     for (int p = 0; p < NP + WB_MAXC; p++) acc[p] = 0.0;
     for (int i = tid; i < n; i += 256) {
-        double r, w, dtyr;
-        wb_row(Pd, S, P, i, any, ep, r, w, dtyr);
+        double r, w, dtyr, swg;
+        wb_row(Pd, S, P, C, i, any, ep, r, w, dtyr, swg);
         double d[WB_MAXC + 1];
 #pragma unroll
-        for (int a = 0; a < WB_MAXC; a++) d[a] = a < m ? wb_deriv(Pd, kd[a], ix[a], i, dtyr) : 0.0;
+        for (int a = 0; a < WB_MAXC; a++) d[a] = a < m ? wb_deriv(Pd, kd[a], ix[a], i, dtyr, swg) : 0.0;
         d[WB_MAXC] = r;
         int p = 0;
 #pragma unroll
@@ -2392,13 +2428,13 @@ __global__ __launch_bounds__(256) void k_wb_gram(const PsrDev* __restrict__ psrs
         for (int c = 0; c < WB_MAXC; c++) swd[c] = 0.0;
         for (int k = k0 + lane; k < k1; k += 64) {
             const int i = Pd.didx[k];
-            double r, w, dtyr;
-            wb_row(Pd, S, P, i, any, ep, r, w, dtyr);
+            double r, w, dtyr, swg;
+            wb_row(Pd, S, P, C, i, any, ep, r, w, dtyr, swg);
             sw += w;
             cnt += 1.0;
             swr += w * r;
 #pragma unroll
-            for (int c = 0; c < WB_MAXC; c++) swd[c] += c < m ? w * wb_deriv(Pd, kd[c], ix[c], i, dtyr) : 0.0;
+            for (int c = 0; c < WB_MAXC; c++) swd[c] += c < m ? w * wb_deriv(Pd, kd[c], ix[c], i, dtyr, swg) : 0.0;
         }
         sw = wave_sum(sw);
         cnt = wave_sum(cnt);
@@ -5611,6 +5647,7 @@ struct pint_ctx {
     int gvdbg = 0;          // (experiment) k_gram_v phases switched off
     int nsplit = 1;
     double *d_tables = nullptr, *d_phhi = nullptr, *d_phlo = nullptr, *d_ftay = nullptr, *d_delay = nullptr;
+    double* d_swg = nullptr;  // solar-wind geometry per evaluation row (k_sw_geom); null: no instance has NE_SW
     double *d_M = nullptr, *d_rt = nullptr, *d_rp = nullptr, *d_chi2 = nullptr, *d_chi2lin = nullptr;
     double *d_G = nullptr, *d_colsq = nullptr, *d_work = nullptr, *d_dpars = nullptr, *d_errs = nullptr;
     double *d_cov = nullptr, *d_sigL = nullptr, *d_lam = nullptr, *d_chi2g = nullptr;
@@ -6234,7 +6271,7 @@ static void free_instances(pint_ctx* ctx) {
         for (auto p : pss) dfree(*p);
     }
     void** ps[] = {(void**)&ctx->d_inst, (void**)&ctx->d_inst_sorted, (void**)&ctx->d_blk_inst, (void**)&ctx->d_blk_row0, (void**)&ctx->d_tables,
-                   (void**)&ctx->d_phhi, (void**)&ctx->d_phlo, (void**)&ctx->d_ftay, (void**)&ctx->d_delay,
+                   (void**)&ctx->d_phhi, (void**)&ctx->d_phlo, (void**)&ctx->d_ftay, (void**)&ctx->d_delay, (void**)&ctx->d_swg,
                    (void**)&ctx->d_M, (void**)&ctx->d_rt, (void**)&ctx->d_rp, (void**)&ctx->d_chi2, (void**)&ctx->d_istatus, (void**)&ctx->d_rscr,
                    (void**)&ctx->d_G, (void**)&ctx->d_colsq,
                    (void**)&ctx->d_work, (void**)&ctx->d_sigL,
@@ -7291,6 +7328,11 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     HIPCHK(cmalloc((void**)&ctx->d_phlo, sizeof(double) * roff));
     HIPCHK(cmalloc((void**)&ctx->d_ftay, sizeof(double) * roff));
     HIPCHK(cmalloc((void**)&ctx->d_delay, sizeof(double) * roff));
+    {
+        bool sw = false;
+        for (int pi : ctx->upsr) sw = sw || ctx->psrs[pi].spec.o_NE_SW >= 0;
+        if (sw) HIPCHK(cmalloc((void**)&ctx->d_swg, sizeof(double) * roff));
+    }
     HIPCHK(cmalloc((void**)&ctx->d_M, sizeof(double) * (moff > 0 ? moff : 1)));
     HIPCHK(cmalloc((void**)&ctx->d_rt, sizeof(double) * out));
     HIPCHK(cmalloc((void**)&ctx->d_rp, sizeof(double) * out));
@@ -7430,6 +7472,19 @@ static void launch_prep(pint_ctx* ctx, double* tables, const double* tables0, In
         hipLaunchKernelGGL(k_prep, dim3(ctx->ninst), dim3(PREP_T), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, tables,
                            tables0, ic);
 }
+// The wideband DM kernels read the per-instance constants only for a solar-wind model (the
+// pulsar direction of its geometry): form them here if the tables changed since the last
+// evaluation.  After flush_restore (the tables hold what the constants are formed from).
+static int ensure_ic_solar_wind(pint_ctx* ctx) {
+    if (ctx->ic_valid) return PINT_OK;
+    bool sw = false;
+    for (int pi : ctx->upsr) sw = sw || (ctx->psrs[pi].dev.wb && ctx->psrs[pi].spec.o_NE_SW >= 0);
+    if (!sw) return PINT_OK;
+    launch_prep(ctx, ctx->d_tables, nullptr, ctx->d_ic);
+    HIPCHK(hipGetLastError());
+    ctx->ic_valid = true;
+    return PINT_OK;
+}
 static void launch_apply(pint_ctx* ctx, const double* lam, double lam_u) {
     ctx->tables_fresh = false;
     if (prep_lanes(ctx))
@@ -7492,7 +7547,7 @@ int pint_eval(pint_ctx* ctx, int want_M) {
     record(ctx, want_M ? 2 : 0);
     const double* tabs = ctx->d_tables;
     const InstConst* icp = ctx->d_ic;
-    EvalRestore rs{nullptr, nullptr, nullptr, nullptr};
+    EvalRestore rs{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!ctx->ic_valid) {  // (k_apply refreshes them itself)
         if (ctx->restore_pending && ctx->ic0_valid) {
             // restore: the evaluation reads the snapshot and its constants (pint_save_tables) and
@@ -7516,10 +7571,17 @@ int pint_eval(pint_ctx* ctx, int want_M) {
     // point's spin part
     const bool spin_pass = want_M && ctx->spin_grid && ctx->tables_fresh && ctx->spin_eval && rs.tables == nullptr &&
                            !ctx->efz && ctx->d_shr && ctx->blk_off[PINT_NBIN] == ctx->blk_off[1];
+    if (ctx->d_swg) {  // SolarWindDispersion: the rows' geometry at these constants, read by the evaluation
+        // (the shared head reads the first point's rows only)
+        hipLaunchKernelGGL(k_sw_geom, dim3(spin_pass ? 1 : ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream,
+                           ctx->d_psrs, ctx->d_inst, icp, ctx->d_swg);
+        HIPCHK(hipGetLastError());
+        rs.swg = ctx->d_swg;
+    }
     if (spin_pass) {
         const int n1 = ctx->inst[0].n + 1;
         hipLaunchKernelGGL(k_eval_head, dim3((n1 + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                           tabs, icp, ctx->d_shr);
+                           tabs, icp, rs.swg, ctx->d_shr);
         hipLaunchKernelGGL(k_eval_spin, dim3((ctx->ninst + 3) / 4), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
                            ctx->ninst, tabs, icp, ctx->d_shr, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay,
                            ctx->d_M);
@@ -7693,8 +7755,9 @@ int pint_dm_resids(pint_ctx* ctx, int subtract_mean, int use_weighted_mean, doub
         HIPCHK(hipMalloc((void**)&ctx->d_dmc2, sizeof(double) * ctx->ninst));
         ctx->dmc2_cap = ctx->ninst;
     }
+    if (int rc = ensure_ic_solar_wind(ctx)) return rc;
     hipLaunchKernelGGL(k_dm_resid, dim3(ctx->ninst), dim3(DMR_T), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                       ctx->d_tables, subtract_mean, use_weighted_mean, ctx->d_dmr, ctx->d_dmc2);
+                       ctx->d_tables, ctx->d_ic, subtract_mean, use_weighted_mean, ctx->d_dmr, ctx->d_dmc2);
     HIPCHK(hipGetLastError());
     if (resid_out) HIPCHK(d2h(resid_out, ctx->d_dmr, sizeof(double) * ctx->tot_out, ctx->stream));
     if (chi2_out) HIPCHK(d2h(chi2_out, ctx->d_dmc2, sizeof(double) * ctx->ninst, ctx->stream));
@@ -7735,9 +7798,10 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
             const pint_spec_t& sp = ctx->psrs[pi].spec;
             if (!ctx->psrs[pi].dev.wb) continue;
             int m = 0;
-            for (int c = 0; c < sp.ncol; c++) m += (sp.col_kind[c] == PINT_COL_DM || sp.col_kind[c] == PINT_COL_ZERO);
+            for (int c = 0; c < sp.ncol; c++)
+                m += (sp.col_kind[c] == PINT_COL_DM || sp.col_kind[c] == PINT_COL_ZERO || sp.col_kind[c] == PINT_COL_NESW);
             if (m > WB_MAXC) {
-                ctx->err = "wideband fit: more than 8 free DM-type columns (DM Taylor terms + DMJUMPs)";
+                ctx->err = "wideband fit: more than 8 free DM-type columns (DM Taylor terms + DMJUMPs + NE_SW)";
                 return PINT_E_INVALID;
             }
         }
@@ -7966,8 +8030,9 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         record(ctx, 15);
     }
     if (ctx->wbfit && cmp) {  // WidebandTOAFitter: the DM rows join the normal equations
+        if (int rc = ensure_ic_solar_wind(ctx)) return rc;
         hipLaunchKernelGGL(k_wb_gram, dim3(ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                           ctx->d_tables, ctx->nsplit, ctx->d_G, ctx->d_colsq, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
+                           ctx->d_tables, ctx->d_ic, ctx->nsplit, ctx->d_G, ctx->d_colsq, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
         HIPCHK(hipGetLastError());
     }
     record(ctx, 7);

@@ -83,7 +83,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         return offs[name]
 
     for s in ("o_F", "o_PEPOCH", "o_lon", "o_lat", "o_pmlon", "o_pmlat", "o_px", "o_POSEPOCH", "o_DM",
-              "o_DMEPOCH", "o_DMX", "o_FD", "o_JUMP", "o_PHOFF", "o_DMJUMP"):
+              "o_DMEPOCH", "o_DMX", "o_FD", "o_JUMP", "o_PHOFF", "o_DMJUMP", "o_NE_SW"):
         setattr(spec, s, -1)
     for i in range(L.B_NPAR):
         spec.o_bin[i] = -1
@@ -117,6 +117,12 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
             spec.shapiro = 2 if ("PLANET_SHAPIRO" in model and model.PLANET_SHAPIRO.value) else 1
         if ak == 2:
             spec.obliquity = OBLIQUITY[str(model.ECL.value or "IERS2010")]
+    if model.has_solar_wind:
+        # SolarWindDispersion, SWM 0 (validate refuses the others); NE_SW zero and frozen is
+        # the reference's all-zeros case and gets no slot: nothing on the device changes
+        if not ak:
+            raise ValueError("SolarWindDispersion needs an astrometry component (the pulsar direction)")
+        spec.o_NE_SW = place("NE_SW")
     dms = model.dm_terms()
     spec.ndm = len(dms)
     if dms:
@@ -188,7 +194,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
     noise_amp = {"TNREDAMP", "TNREDGAM", "TNREDC", "RNAMP", "RNIDX", "TNDMAMP", "TNDMGAM", "TNDMC"}
     # parameter -> (column kind, index), built once per layout (a PTA pulsar has ~115 free
     # parameters, 100 of them DMX: list.index per parameter was a quadratic scan)
-    kind_of = {"PHOFF": (L.COL_OFFSET, 0), "PX": (L.COL_PX, 0)}  # (PHOFF: -d_offset_phase_d_PHOFF / F0 = 1/F0)
+    kind_of = {"PHOFF": (L.COL_OFFSET, 0), "PX": (L.COL_PX, 0), "NE_SW": (L.COL_NESW, 0)}  # (PHOFF: -d_offset_phase_d_PHOFF / F0 = 1/F0)
     for names, kk in ((("RAJ", "ELONG"), L.COL_LON), (("DECJ", "ELAT"), L.COL_LAT), (("PMRA", "PMELONG"), L.COL_PMLON),
                       (("PMDEC", "PMELAT"), L.COL_PMLAT)):
         for nm in names:

@@ -207,7 +207,7 @@ _DEFS = {
 _ALIASES = {
     "RA": "RAJ", "DEC": "DECJ", "LAMBDA": "ELONG", "BETA": "ELAT", "PMLAMBDA": "PMELONG",
     "PMBETA": "PMELAT", "E": "ECC", "ECCDOT": "EDOT", "XDOT": "A1DOT", "T2EFAC": "EFAC",
-    "T2EQUAD": "EQUAD", "TNECORR": "ECORR", "SOLARN0": "NE_SW", "CLK": "CLOCK", "PSRJ": "PSR", "PSRB": "PSR", "VARSIGMA": "STIGMA", "STIG": "STIGMA",
+    "T2EQUAD": "EQUAD", "TNECORR": "ECORR", "SOLARN0": "NE_SW", "NE1AU": "NE_SW", "CLK": "CLOCK", "PSRJ": "PSR", "PSRB": "PSR", "VARSIGMA": "STIGMA", "STIG": "STIGMA",
 }
 
 _PREFIX = {  # prefix params: regex -> (component, units template, long_double)

@@ -22,10 +22,12 @@ categories follow its component-type insertion order, a set iteration in ``model
 so the reference itself does not fix it), each component's parameters in the reference
 component's own order.
 
-Defaults the reference's components carry but this path does not model (SOLARN0, SWM,
-CORRECT_TROPOSPHERE, PLANET_SHAPIRO N, DILATEFREQ, TIMEEPH, T2CMETHOD, ...) are not
+Defaults the reference's components carry but the par file did not name
+(CORRECT_TROPOSPHERE, PLANET_SHAPIRO N, DILATEFREQ, TIMEEPH, T2CMETHOD, ...) are not
 written; reading the file back with the reference gives them their default values, the
-same values the reference would have written.
+same values the reference would have written.  A model with SolarWindDispersion writes
+NE_SW (fit flag and uncertainty like any fitted parameter) and SWM as the reference's
+``print_par`` does (``solar_wind_dispersion.py:453-459``; SWP belongs to SWM 1 only).
 """
 from __future__ import annotations
 

@@ -92,6 +92,9 @@ class TimingModel:
         # one stable sort by group rank (dict order within a group): top level, astrometry,
         # spindown, the delay/phase/noise components in order, the rest
         order = [("Binary" if c.startswith("Binary") else c) for c in DELAY_ORDER]
+        # DispersionJump (dispersion_jump) precedes the binary (pulsar_system) in the reference's
+        # DEFAULT_ORDER (timing_model.py:107-123), which orders its delay components' parameters
+        order.insert(order.index("Binary"), "DispersionJump")
         rest = {}
         for comp in dict.fromkeys(order + ["AbsPhase", "PhaseJump"] + NOISE):
             if not comp.startswith("Astrometry"):
@@ -157,6 +160,12 @@ class TimingModel:
             return 2
         return 0
 
+    @property
+    def has_solar_wind(self) -> bool:
+        """SolarWindDispersion with something to evaluate: NE_SW free or non-zero (the
+        reference's delay and DM are zeros when NE_SW == 0, solar_wind_dispersion.py:378-392)."""
+        return "NE_SW" in self._params and (not self.NE_SW.frozen or bool(self.NE_SW.value))
+
     def _names_of(self, key, build):
         """Name lists derived from the parameter set alone, cached until the next add_param
         (parameters are never removed): build_layout / validate ask for them many times per
@@ -217,10 +226,12 @@ class TimingModel:
             if len(self.dm_terms()) > 1 and any(self[n].value for n in self.dm_terms()[1:]):
                 if self.DMEPOCH.value is None:
                     self.DMEPOCH.value = LD(self.PEPOCH.value)  # dispersion_model.py:197
-        if "NE_SW" in self and self.NE_SW.value:
-            raise NotImplementedError("solar-wind dispersion (NE_SW != 0) is outside the supported hot path")
+        if self.has_solar_wind and int(self.SWM.value or 0) != 0:
+            # SWM 1 (the power-law index SWP; solar_wind_dispersion.py:361-364) is not modelled
+            raise NotImplementedError(f"solar-wind dispersion with SWM {self.SWM.value} is outside the supported "
+                                      "hot path (SWM 0 only)")
         if "CORRECT_TROPOSPHERE" in self and self.CORRECT_TROPOSPHERE.value:
-            raise NotImplementedError("troposphere delay is outside the supported hot path")
+            raise NotImplementedError("troposphere delay (CORRECT_TROPOSPHERE Y) is outside the supported hot path")
         if self.binary in ("DD", "BT", "DDK"):
             e = float(self.ECC.value or 0.0)
             if not (0 <= e < 1):
@@ -361,7 +372,7 @@ def get_model(parfile) -> TimingModel:
     defaults += [("DILATEFREQ", False), ("DMDATA", False), ("NTOA", 0), ("UNITS", "TDB")]
     if has_eq or has_ecl:
         defaults += [("PLANET_SHAPIRO", False)]
-    if any(n in ("NE_SW", "SOLARN0") for n in names):
+    if any(n in ("NE_SW", "SOLARN0", "NE1AU") for n in names):
         defaults += [("SWM", 0)]
     if any(n == "DM" or re.match(r"^DM\d+$", n) for n in names):
         defaults += [("DM", LD(0)), ("DMEPOCH", None)]
