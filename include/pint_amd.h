@@ -41,6 +41,7 @@ extern "C" {
 #define PINT_MAX_DMK 10
 #define PINT_MAX_FD 10
 #define PINT_MAX_JUMP 64
+#define PINT_MAX_GLITCH 64    /* glitches per model (the JUMP cap; J0537-6910 has more than 32) */
 
 /* ---- per-TOA packed input (reference TOAs.table columns
  *      toa.py:2320 tdbld, :2385-2439 posvels, freq, error, mjd_float, pulse_number) ---- */
@@ -102,8 +103,16 @@ enum {
     PINT_COL_PMLON = 4, PINT_COL_PMLAT = 5, PINT_COL_PX = 6, PINT_COL_DM = 7,
     PINT_COL_DMX = 8, PINT_COL_FD = 9, PINT_COL_JUMP = 10, PINT_COL_BIN = 11,
     PINT_COL_ZERO = 12,     /* a parameter without a delay (DMJUMP, dispersion_model.py:797) */
-    PINT_COL_NESW = 13      /* NE_SW: d_delay_d_ne_sw = DMconst * solar_wind_geometry / bfreq^2
+    PINT_COL_NESW = 13,     /* NE_SW: d_delay_d_ne_sw = DMconst * solar_wind_geometry / bfreq^2
                                (solar_wind_dispersion.py:404-412), d_dm_d_ne_sw = the geometry (:394) */
+    PINT_COL_GLITCH = 14    /* a Glitch parameter: col_index = 7 * glitch + PINT_GL_*; -d_phase_d_p / F0
+                               on the TOAs the glitch acts on, 0 elsewhere (glitch.py:234-344); a timing
+                               column like any other (its wideband DM rows are zero)                 */
+};
+/* the parameters of one glitch, in the order of its 7 table slots (glitch.py:130-138 glitch_prop) */
+enum {
+    PINT_GL_EP = 0, PINT_GL_PH, PINT_GL_F0, PINT_GL_F1, PINT_GL_F2, PINT_GL_F0D, PINT_GL_TD,
+    PINT_GL_NPAR
 };
 /* binary parameter ids (stand_alone_psr_binaries/binary_generic.py, ELL1_model.py, DD_model.py,
  * ELL1H_model.py (H3, H4, STIGMA), DDK_model.py (KIN, KOM)) */
@@ -163,7 +172,17 @@ typedef struct {
                                (:356-360, astrometry.py:114-150; Edwards et al. 2006 eq. 29-30);
                                its delay joins the sum after the Solar-system Shapiro delay and
                                before DispersionDM (timing_model.py DEFAULT_ORDER)              */
-    int32_t rsv_;           /* unused reserve (keeps the header a whole number of doubles)      */
+    int32_t o_GLITCH;       /* Glitch: table slot of the first glitch's block (-1 none).  Glitch k has 7
+                               dd pairs at o_GLITCH + 14 k, in PINT_GL_* order and par units (GLEP MJD,
+                               GLPH cycles, GLF0 Hz, GLF1 Hz/s, GLF2 Hz/s^2, GLF0D Hz, GLTD d).  With
+                               dt = (tdb - GLEP) 86400 s - delay (the model's total delay), on the rows
+                               with dt > 0 the phase gains GLPH + dt (GLF0 + dt GLF1 / 2 + dt^2 GLF2 / 6)
+                               + GLF0D tau (1 - exp(-dt / tau)), tau = GLTD 86400 s, the last term only
+                               when GLF0D != 0 (glitch.py:193-232); the TZR TOA like any TOA.  Glitch
+                               registers no phase_derivs_wrt_delay (only spindown.py:85 does), so the
+                               chain factor of the delay columns is unchanged                      */
+    int32_t nglitch;        /* glitches (<= PINT_MAX_GLITCH), in ascending index                  */
+    int32_t rsv_[3];        /* unused reserve (keeps the header a whole number of 16-byte words)  */
     int32_t col_kind[PINT_MAX_COLS];
     int32_t col_index[PINT_MAX_COLS];
     int32_t col_toff[PINT_MAX_COLS];  /* table offset of the column's parameter (-1: Offset) */
@@ -403,7 +422,7 @@ int pint_check_step(pint_ctx *ctx, int slot);
  * lane per instance (64 instances per wave) instead of one wave per instance. */
 #define PINT_OPT_LANE_SOLVE 13
 /* PINT_OPT_SPIN_EVAL = 1 (default, env PINT_SPIN_EVAL): a pint_set_grid batch whose points
- * differ in spin frequencies only (isolated model, no red-noise basis) evaluates its rows'
+ * differ in spin frequencies or glitch parameters only (isolated model, no red-noise basis) evaluates its rows'
  * delays and astrometric geometry once, on the first point, for the evaluation with the
  * design matrix that precedes the first fit step; each point then runs the spin part only.
  * The same bits as the full evaluation. */
@@ -446,9 +465,11 @@ int pint_capture_end(pint_ctx *ctx);
 int pint_graph_launch(pint_ctx *ctx);
 /* Introspection: PINT_QUERY_NVGRAM = 1 returns the number of instances of the current batch
  * on the generated-Fourier path, PINT_QUERY_NSPLIT = 2 the Gram's N-split count (row blocks
- * per instance); negative status on error. */
+ * per instance), PINT_QUERY_NSPINEVAL = 3 the number of evaluations of this context that took
+ * the shared head of a spin-only grid (PINT_OPT_SPIN_EVAL); negative status on error. */
 #define PINT_QUERY_NVGRAM 1
 #define PINT_QUERY_NSPLIT 2
+#define PINT_QUERY_NSPINEVAL 3
 int pint_query(pint_ctx *ctx, int key);
 /* Page-locked host memory for the output buffers (hipHostMalloc); NULL on failure. */
 void *pint_host_alloc(size_t bytes);

@@ -19,7 +19,9 @@ NSLOT = 4  # pipeline slots (pint_step_end / pint_check_step): set from the libr
 B_NPAR = 27
 BIN_NONE, BIN_ELL1, BIN_DD, BIN_ELL1H, BIN_BT, BIN_DDK = range(6)
 
-COL_OFFSET, COL_F, COL_LON, COL_LAT, COL_PMLON, COL_PMLAT, COL_PX, COL_DM, COL_DMX, COL_FD, COL_JUMP, COL_BIN, COL_ZERO, COL_NESW = range(14)
+COL_OFFSET, COL_F, COL_LON, COL_LAT, COL_PMLON, COL_PMLAT, COL_PX, COL_DM, COL_DMX, COL_FD, COL_JUMP, COL_BIN, COL_ZERO, COL_NESW, COL_GLITCH = range(15)
+MAX_GLITCH = 64  # PINT_MAX_GLITCH
+GL_NPAR = 7      # PINT_GL_NPAR: GLEP, GLPH, GLF0, GLF1, GLF2, GLF0D, GLTD (col_index = 7 * glitch + which)
 
 PINT_OK, PINT_E_INVALID, PINT_E_HIP, PINT_E_NOT_PD, PINT_E_KEPLER, PINT_E_PARAM, PINT_E_SIGMA = range(7)
 
@@ -47,7 +49,7 @@ class SpecT(C.Structure):
                                           "track_pn", "subtract_mean", "weighted_mean", "ncol", "nred", "tstride",
                                           "o_F", "o_PEPOCH", "o_lon", "o_lat", "o_pmlon", "o_pmlat", "o_px",
                                           "o_POSEPOCH", "o_DM", "o_DMEPOCH", "o_DMX", "o_FD", "o_JUMP")] + [
-        ("o_bin", C.c_int32 * B_NPAR), ("o_PHOFF", C.c_int32), ("wb_noones", C.c_int32), ("ell1h", C.c_int32), ("nharms", C.c_int32), ("dmn0", C.c_int32), ("k96", C.c_int32), ("o_DMJUMP", C.c_int32), ("ndmjump", C.c_int32), ("obliquity", C.c_double), ("red_f0", C.c_double), ("o_NE_SW", C.c_int32), ("rsv_", C.c_int32),
+        ("o_bin", C.c_int32 * B_NPAR), ("o_PHOFF", C.c_int32), ("wb_noones", C.c_int32), ("ell1h", C.c_int32), ("nharms", C.c_int32), ("dmn0", C.c_int32), ("k96", C.c_int32), ("o_DMJUMP", C.c_int32), ("ndmjump", C.c_int32), ("obliquity", C.c_double), ("red_f0", C.c_double), ("o_NE_SW", C.c_int32), ("o_GLITCH", C.c_int32), ("nglitch", C.c_int32), ("rsv_", C.c_int32 * 3),
         ("col_kind", C.c_int32 * MAX_COLS), ("col_index", C.c_int32 * MAX_COLS), ("col_toff", C.c_int32 * MAX_COLS)]
 
 

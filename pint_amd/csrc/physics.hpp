@@ -1139,6 +1139,80 @@ PD void eval_spin_a(const pint_spec_t& S, const double* P, const InstConst& C, c
     sp.chain = o.fdt * C.iF0;  // M = -(d_phase_d_delay * d_delay_d_p)/F0, d_phase_d_delay = -F(dt)
 }
 
+// Glitch (glitch.py:193-344), a pass of its own after the evaluation (k_glitch): formed inside
+// eval_spin_b its exp and divisions raised the registers of the evaluation's builds (isolated
+// with M 87 -> 107 VGPRs and 5 -> 4 waves/SIMD, k_eval_spin 103 -> 129 and 4 -> 3, ELL1 without M
+// 6 -> 5; a non-inlined helper cost more), so glitch_row_phase / glitch_row_columns run on the
+// evaluation's outputs instead.
+// dt of glitch k at a row: (tdb - GLEP_k) 86400 s - delay (the model's total delay), formed in
+// dd (the epoch difference is exact there) and rounded once; the glitch acts where dt > 0.  The
+// phase and every column of the glitch call this one function, so they take the same dt and the
+// same decision.
+PD double glitch_dt(const pint_spec_t& S, const double* P, dd tdb, double delay, int k) {
+    const int o = S.o_GLITCH + 2 * PINT_GL_NPAR * k;
+    return dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(P, o + 2 * PINT_GL_EP)), DAYSEC), -delay));
+}
+// glitch_phase (:193-232) of one glitch at dt > 0, in double: at Vela's sizes (2e3 cycles,
+// dt 1e8 s) its rounding is 1e-13 cycle
+PD double glitch_phase_at(const double* G, double dt) {
+    double ph = pval(G, 2 * PINT_GL_PH) +
+                dt * (pval(G, 2 * PINT_GL_F0) +
+                      dt * (0.5 * pval(G, 2 * PINT_GL_F1) + dt * ((1.0 / 6.0) * pval(G, 2 * PINT_GL_F2))));
+    const double f0d = pval(G, 2 * PINT_GL_F0D);
+    if (f0d != 0.0) {
+        const double tau = pval(G, 2 * PINT_GL_TD) * DAYSEC;
+        ph += f0d * tau * (1.0 - exp(-dt / tau));
+    }
+    return ph;
+}
+// -d_phase_d_p / F0 of one glitch parameter at dt > 0, per par unit (GLEP and GLTD per day)
+// (d_phase_d_GLPH ... d_phase_d_GLEP, :244-344)
+PD double glitch_col_at(const double* G, int which, double dt, double iF0) {
+    const double tau = pval(G, 2 * PINT_GL_TD) * DAYSEC;
+    const double f0d = pval(G, 2 * PINT_GL_F0D);
+    const double e = tau != 0.0 ? exp(-dt / tau) : 0.0;
+    double d;
+    switch (which) {
+        case PINT_GL_PH: d = 1.0; break;
+        case PINT_GL_F0: d = dt; break;
+        case PINT_GL_F1: d = 0.5 * dt * dt; break;
+        case PINT_GL_F2: d = (1.0 / 6.0) * dt * dt * dt; break;
+        case PINT_GL_F0D: d = tau * (1.0 - e); break;
+        case PINT_GL_TD:  // zeros when GLTD == 0 (:315)
+            d = tau != 0.0 ? (f0d * (1.0 - e) - f0d * e * (dt / tau)) * DAYSEC : 0.0;
+            break;
+        default:  // PINT_GL_EP; the decay term only when tau != 0 (:342)
+            d = -(pval(G, 2 * PINT_GL_F0) +
+                  dt * (pval(G, 2 * PINT_GL_F1) + 0.5 * dt * pval(G, 2 * PINT_GL_F2)) + f0d * e) * DAYSEC;
+    }
+    return -d * iF0;
+}
+
+// Glitch.glitch_phase (glitch.py:193-232) added to a row's phase: the glitches' phases add, on
+// the TZR row as on any TOA
+PD dd glitch_row_phase(const pint_spec_t& S, const double* P, dd tdb, double delay, dd ph) {
+    for (int k = 0; k < S.nglitch; k++) {
+        const double gdt = glitch_dt(S, P, tdb, delay, k);
+        if (gdt > 0.0) ph = dd_add_d(ph, glitch_phase_at(P + S.o_GLITCH + 2 * PINT_GL_NPAR * k, gdt));
+    }
+    return ph;
+}
+// the PINT_COL_GLITCH columns of design-matrix row r (Mb, ld, runs, compact as in eval_spin_b):
+// exactly 0 where the glitch does not act.  A run lies within one glitch or crosses into the next.
+PD void glitch_row_columns(const pint_spec_t& S, const double* P, dd tdb, double delay, double iF0, double* Mb,
+                           unsigned r, long ld, const ColRun* runs, int nrun, bool compact) {
+    for (int u = 0; u < nrun; u++) {
+        const ColRun R = runs[u];
+        if (R.kind != PINT_COL_GLITCH) continue;
+        double* colp = Mb + (long)(compact ? R.dcol0 : R.col0) * ld;
+        for (int j = 0; j < R.cnt; j++, colp += ld) {
+            const int k = (R.idx0 + j) / PINT_GL_NPAR, which = (R.idx0 + j) - PINT_GL_NPAR * k;
+            const double gdt = glitch_dt(S, P, tdb, delay, k);
+            colp[r] = gdt > 0.0 ? glitch_col_at(P + S.o_GLITCH + 2 * PINT_GL_NPAR * k, which, gdt, iF0) : 0.0;
+        }
+    }
+}
+
 // eval_toa's spindown phase, jumps and PhaseOffset, then the design-matrix row but for the
 // binary columns (written by eval_toa while the binary state is live)
 template <int BIN>
@@ -1231,7 +1305,7 @@ PD void eval_spin_b(const pint_spec_t& S, const double* P, const InstConst& C, c
                 if (BIN == 0)
                     for (int j = 0; j < R.cnt; j++, colp += ld) colp[r] = 0.0;
                 break;
-            default:
+            default:  // (PINT_COL_GLITCH too: k_glitch then writes those columns, glitch_row_columns)
                 for (int j = 0; j < R.cnt; j++, colp += ld) colp[r] = 0.0;
         }
     }

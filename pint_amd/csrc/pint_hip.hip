@@ -641,6 +641,36 @@ __global__ __launch_bounds__(256) void k_sw_geom(const PsrDev* __restrict__ psrs
     swg[I.roff + r] = sw_geometry_row(Pd, ic[blockIdx.x], r);
 }
 
+// k_glitch: the Glitch component (glitch.py:193-344) of the instances whose model has glitches,
+// after the evaluation, on its outputs: every evaluation row's phase (TOAs and the TZR row)
+// gains the glitch phase at the row's total delay, and with Mout the PINT_COL_GLITCH columns of
+// the TOAs' rows are written (the evaluation leaves them alone), in the full or the compact fit
+// layout.  A pass of its own because inside k_eval / k_eval_spin the exp and the divisions cost
+// those builds registers and occupancy (physics.hpp); a batch with glitches therefore runs its
+// residual pass after this kernel, not fused into the evaluation.  The same tables and
+// per-instance constants as the evaluation.  One thread per row; grid (instances, row blocks
+// of the longest instance); ~50 B/row plus 8 B per free glitch column.
+__global__ __launch_bounds__(256) void k_glitch(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
+                                                const double* __restrict__ tables, const InstConst* __restrict__ ic,
+                                                const double* __restrict__ delay, double* __restrict__ ph_hi,
+                                                double* __restrict__ ph_lo, double* __restrict__ Mout, int compact) {
+    const InstDev I = insts[blockIdx.x];
+    const PsrDev& Pd = psrs[I.psr];
+    const pint_spec_t& S = *Pd.spec;
+    if (S.nglitch <= 0) return;  // (block-uniform)
+    const int r = blockIdx.y * 256 + threadIdx.x;
+    if (r > I.n) return;
+    const double* P = tables + I.toff;
+    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
+    const double dl = delay[I.roff + r];
+    const dd ph = glitch_row_phase(S, P, tdb, dl, dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]));
+    ph_hi[I.roff + r] = ph.hi;
+    ph_lo[I.roff + r] = ph.lo;
+    if (Mout && r < I.n)
+        glitch_row_columns(S, P, tdb, dl, ic[blockIdx.x].iF0, Mout + I.moff, (unsigned)r, I.n, Pd.runs, Pd.nrun,
+                           compact && Pd.dsplit);
+}
+
 // Spin-only grids (pint_set_grid's variables all spin frequencies, isolated model, no
 // red-noise basis, the full layout): before the first fit step every point shares its
 // delays, astrometric geometry and dispersion factors (they depend on the TOAs and the
@@ -5627,12 +5657,14 @@ struct pint_ctx {
     double* d_rpart = nullptr;    // per residual block: sum w, sum w x, chi2 partial
     double* d_epart = nullptr;    // fused residual pass (efz): per evaluation block sum w, sum w x
     int efz = 0;                  // the batch's evaluation blocks carry k_resid1 (EF_ROWS rows + row 0 + TZR)
+    bool any_glitch = false;      // an instance's model has glitches: k_glitch follows the evaluation
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
     int spin_grid = 0;            // the resident grid's points differ in spin parameters only (k_eval_head/_spin)
     bool tables_fresh = false;    // ... and the tables are still pint_set_grid's (no step applied since)
     int spin_eval = 1;            // PINT_SPIN_EVAL: use the shared head for such grids
+    int n_spin_eval = 0;          // evaluations that took it (PINT_QUERY_NSPINEVAL)
     double* d_shr = nullptr;      // its rows (EVAL_HEAD_W doubles each)
     long shr_cap = 0;
     int nrblk = 0;
@@ -6517,6 +6549,10 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
     if (Kp > GMAXKP) { ctx->err = "design matrix too wide for k_gram (K+1 > 256)"; return -PINT_E_INVALID; }
     if (spec->njump > PINT_MAX_JUMP) { ctx->err = "too many JUMPs"; return -PINT_E_INVALID; }
     if (spec->ndmjump < 0 || spec->ndmjump > 64) { ctx->err = "too many DMJUMPs"; return -PINT_E_INVALID; }
+    if (spec->nglitch < 0 || spec->nglitch > PINT_MAX_GLITCH || (spec->nglitch > 0 && spec->o_GLITCH < 0)) {
+        ctx->err = "bad glitch count or table slot (PINT_MAX_GLITCH)";
+        return -PINT_E_INVALID;
+    }
     if (spec->binary < 0 || spec->binary > PINT_BIN_DDK) { ctx->err = "unsupported binary model"; return -PINT_E_INVALID; }
     if (spec->binary == PINT_BIN_ELL1H &&
         (spec->ell1h < 1 || spec->ell1h > 3 || (spec->ell1h == 2 && (spec->nharms < 3 || spec->nharms > 64)))) {
@@ -6876,7 +6912,11 @@ int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar
         const PsrHost& ph = ctx->psrs[psr];
         const pint_spec_t& sp = ph.spec;
         bool spin = nvar > 0 && sp.binary == 0 && sp.nred == 0 && !ph.dev.dsplit && !ctx->efz;
-        for (int j = 0; j < nvar; j++) spin = spin && var_toff[j] >= sp.o_F && var_toff[j] < sp.o_F + 2 * sp.nf;
+        // (a glitch parameter is as phase-only as an F term: the head does not depend on it)
+        for (int j = 0; j < nvar; j++)
+            spin = spin && ((var_toff[j] >= sp.o_F && var_toff[j] < sp.o_F + 2 * sp.nf) ||
+                            (sp.nglitch > 0 && var_toff[j] >= sp.o_GLITCH &&
+                             var_toff[j] < sp.o_GLITCH + 2 * PINT_GL_NPAR * sp.nglitch));
         ctx->spin_grid = spin;
         if (spin && (long)(ph.n + 1) * EVAL_HEAD_W > ctx->shr_cap) {
             dfree((void*&)ctx->d_shr);
@@ -6913,7 +6953,10 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     }
     // the fused residual pass for batches off the small-instance path (whose one-wave
     // residual kernels serve instances of <= RES_SMALLN rows)
-    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN);
+    // (not for a batch with glitches: their phase is added after the evaluation, by k_glitch)
+    ctx->any_glitch = false;
+    for (int k = 0; k < ninst; k++) ctx->any_glitch = ctx->any_glitch || ctx->psrs[inst_psr[k]].spec.nglitch > 0;
+    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch;
     long ebn = 0;
     // N-split for the Gram so the launch fills the 256 CUs
     // choose the split count that minimises (workgroup rounds) / nsplit, i.e. the k_gram
@@ -7586,6 +7629,7 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                            ctx->ninst, tabs, icp, ctx->d_shr, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay,
                            ctx->d_M);
         HIPCHK(hipGetLastError());
+        ctx->n_spin_eval++;
     }
     // a batch of one model (a grid's points, an all-isolated PTA) takes that model's own
     // build, whose register set the other models do not raise (k_eval<WM, 0>: 48 instead
@@ -7659,6 +7703,12 @@ int pint_eval(pint_ctx* ctx, int want_M) {
             }
         }
 #undef PINT_EVAL_LAUNCH
+        HIPCHK(hipGetLastError());
+    }
+    if (ctx->any_glitch) {  // Glitch: the phase of every row and the glitch columns, on the evaluation's outputs
+        hipLaunchKernelGGL(k_glitch, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
+                           want_M == 2 ? 1 : 0);
         HIPCHK(hipGetLastError());
     }
     record(ctx, want_M ? 3 : 1);
@@ -8600,6 +8650,7 @@ int pint_query(pint_ctx* ctx, int key) {
     if (!ctx) return -PINT_E_INVALID;
     if (key == PINT_QUERY_NVGRAM) return ctx->n_vg;
     if (key == PINT_QUERY_NSPLIT) return ctx->nsplit;
+    if (key == PINT_QUERY_NSPINEVAL) return ctx->n_spin_eval;
     ctx->err = "unknown query";
     return -PINT_E_INVALID;
 }

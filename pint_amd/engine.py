@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib as L
 from .noise import red_noise_freqs_weights, scaled_sigma_us
 from .parameter import LD
-from .timing_model import BIN_IDS, OBLIQUITY, TimingModel
+from .timing_model import BIN_IDS, GLITCH_PROPS, OBLIQUITY, TimingModel
 
 UNITS = {  # design-matrix column units as the reference prints them (per par unit / F0)
     "RAJ": "1 / (hourangle Hz)", "DECJ": "1 / (deg Hz)", "ELONG": "1 / (deg Hz)", "ELAT": "1 / (deg Hz)",
@@ -83,7 +83,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         return offs[name]
 
     for s in ("o_F", "o_PEPOCH", "o_lon", "o_lat", "o_pmlon", "o_pmlat", "o_px", "o_POSEPOCH", "o_DM",
-              "o_DMEPOCH", "o_DMX", "o_FD", "o_JUMP", "o_PHOFF", "o_DMJUMP", "o_NE_SW"):
+              "o_DMEPOCH", "o_DMX", "o_FD", "o_JUMP", "o_PHOFF", "o_DMJUMP", "o_NE_SW", "o_GLITCH"):
         setattr(spec, s, -1)
     for i in range(L.B_NPAR):
         spec.o_bin[i] = -1
@@ -151,6 +151,20 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         spec.o_JUMP = pos
         for n in jumps:
             place(n)
+    # Glitch: one block of 7 slots per glitch, in ascending index and GLITCH_PROPS order
+    # (setup_glitches filled the missing ones); a glitch whose amplitudes are all zero and
+    # frozen keeps its slots
+    glitches = model.glitch_indices()
+    spec.nglitch = len(glitches)
+    if len(glitches) > L.MAX_GLITCH:
+        raise NotImplementedError(f"more than {L.MAX_GLITCH} glitches (PINT_MAX_GLITCH)")
+    glitch_cols = {}
+    if glitches:
+        spec.o_GLITCH = pos
+        for k, idx in enumerate(glitches):
+            for w, pre in enumerate(GLITCH_PROPS):
+                place(f"{pre}{idx}")
+                glitch_cols[f"{pre}{idx}"] = (L.COL_GLITCH, L.GL_NPAR * k + w)
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
                    "DDK": L.BIN_DDK}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
@@ -199,6 +213,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
                       (("PMDEC", "PMELAT"), L.COL_PMLAT)):
         for nm in names:
             kind_of[nm] = (kk, 0)
+    kind_of.update(glitch_cols)
     # (later groups first, so that an earlier group wins a shared name, as the if-chain did)
     for group, kk in ((dmjumps, L.COL_ZERO), (jumps, L.COL_JUMP), (fds, L.COL_FD), (dmx, L.COL_DMX),
                       (dms, L.COL_DM), (F, L.COL_F)):
@@ -956,6 +971,10 @@ class Session:
     def n_vgram(self):
         """Instances of the current batch on the generated-Fourier compact path."""
         return int(self.L.pint_query(self.ctx, 1))
+
+    def n_spin_eval(self):
+        """Evaluations of this session that took the shared head of a spin-only grid."""
+        return int(self.L.pint_query(self.ctx, 3))
 
     def nsplit(self):
         """The Gram's N-split count of the current batch (row blocks per instance)."""

@@ -217,6 +217,14 @@ _PREFIX = {  # prefix params: regex -> (component, units template, long_double)
     r"^DMXR1_(\d+)$": ("DispersionDMX", "d", True),
     r"^DMXR2_(\d+)$": ("DispersionDMX", "d", True),
     r"^FD(\d+)$": ("FD", "s", False),
+    # Glitch (glitch.py:56-124): the epoch an MJD, the rest float64 in the reference's units
+    r"^GLEP_(\d+)$": ("Glitch", "d", True),
+    r"^GLPH_(\d+)$": ("Glitch", "pulse phase", False),
+    r"^GLF0_(\d+)$": ("Glitch", "Hz", False),
+    r"^GLF1_(\d+)$": ("Glitch", "Hz / s", False),
+    r"^GLF2_(\d+)$": ("Glitch", "Hz / s2", False),
+    r"^GLF0D_(\d+)$": ("Glitch", "Hz", False),
+    r"^GLTD_(\d+)$": ("Glitch", "d", False),
 }
 
 MASK_PARAMS = {"JUMP": ("PhaseJump", "s"), "EFAC": ("ScaleToaError", ""),
@@ -238,7 +246,7 @@ def make_param(name: str) -> Optional[Param]:
         m = re.match(rx, name)
         if m:
             idx = int(m.group(1))
-            kind = "mjd" if name.startswith("DMXR") else "float"
+            kind = "mjd" if name.startswith(("DMXR", "GLEP_")) else "float"
             u = units.replace("{n}", str(idx))
             if name == "F0":
                 u = "Hz"

@@ -28,6 +28,8 @@ written; reading the file back with the reference gives them their default value
 same values the reference would have written.  A model with SolarWindDispersion writes
 NE_SW (fit flag and uncertainty like any fitted parameter) and SWM as the reference's
 ``print_par`` does (``solar_wind_dispersion.py:453-459``; SWP belongs to SWM 1 only).
+A model with glitches writes, per glitch in ascending index, GLEP_ GLPH_ GLF0_ GLF1_ GLF2_
+GLF0D_ GLTD_, the ones ``setup`` filled in with 0 included (``glitch.py:185-191``).
 """
 from __future__ import annotations
 
@@ -242,8 +244,8 @@ _ORDER = {
     "PLDMNoise": ["TNDMAMP", "TNDMGAM", "TNDMC"],
 }
 MIDDLE = ["TroposphereDelay", "SolarSystemShapiro", "SolarWindDispersion", "DispersionDM", "DispersionDMX",
-          "Binary", "FD", "AbsPhase", "PhaseOffset", "PhaseJump", "EcorrNoise", "ScaleToaError", "PLRedNoise",
-          "PLDMNoise"]
+          "Binary", "FD", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise", "ScaleToaError",
+          "PLRedNoise", "PLDMNoise"]
 
 
 def _by_index(names, prefix):
@@ -271,6 +273,9 @@ def _component_params(model, comp: str) -> List[str]:
         ef, eq = _by_index(names, "EFAC"), _by_index(names, "EQUAD")
         head = [n for n in ("EFAC1", "EQUAD1") if n in names]
         return head + [n for n in ef if n not in head] + [n for n in eq if n not in head]
+    if comp == "Glitch":  # Glitch.print_par (glitch.py:185-191): per glitch, in glitch_prop's order
+        from .timing_model import GLITCH_PROPS
+        return [f"{pre}{i}" for i in model.glitch_indices() for pre in GLITCH_PROPS if f"{pre}{i}" in P]
     if comp in _ORDER:
         return [n for n in _ORDER[comp] if n in names] + [n for n in names if n not in _ORDER[comp]]
     return names

@@ -22,8 +22,14 @@ from .parameter import LD, Param
 # components supported on the hot path
 DELAY_ORDER = ["AstrometryEquatorial", "AstrometryEcliptic", "TroposphereDelay", "SolarSystemShapiro",
                "SolarWindDispersion", "DispersionDM", "DispersionDMX", "BinaryELL1", "BinaryDD", "FD"]
-PHASE_ORDER = ["AbsPhase", "Spindown", "PhaseOffset", "PhaseJump"]
+PHASE_ORDER = ["AbsPhase", "Spindown", "Glitch", "PhaseOffset", "PhaseJump"]
 NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
+
+# Glitch (glitch.py): the parameters of one glitch in the order setup / print_par walk them
+# (glitch_prop, :130-138), which is also the order of a glitch's 7 table slots and of
+# PINT_GL_*; and the order the component declares its index-1 parameters in (:56-124)
+GLITCH_PROPS = ("GLEP_", "GLPH_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_")
+GLITCH_DECLARED = ("GLPH_", "GLEP_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_")
 
 ELL1_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "EDOT", "OMDOT", "M2", "SINI", "TASC", "EPS1", "EPS2",
                "EPS1DOT", "EPS2DOT"]
@@ -98,8 +104,8 @@ class TimingModel:
         rest = {}
         for comp in dict.fromkeys(order + ["AbsPhase", "PhaseJump"] + NOISE):
             if not comp.startswith("Astrometry"):
-                rest.setdefault(comp, 3 + len(rest))
-        big = 3 + len(rest)
+                rest.setdefault(comp, 4 + len(rest))
+        big = 4 + len(rest)
 
         def rank(c):
             if c in ("", "TimingModel"):
@@ -108,9 +114,23 @@ class TimingModel:
                 return 1
             if c == "Spindown":
                 return 2
+            if c == "Glitch":  # a phase component: after Spindown, before the delay components
+                return 3
             return rest.get(c, big)
         ranks = {c: rank(c) for c in {p.component for p in self._params.values()}}
-        return sorted(self._params, key=lambda n: ranks[self._params[n].component])
+        if "Glitch" not in ranks:
+            return sorted(self._params, key=lambda n: ranks[self._params[n].component])
+
+        # Glitch's own order (glitch.py:56-153): the index-1 parameters in the order the component
+        # declares them, the other indices in par-file order, then the ones setup filled in
+        # (get_model adds those last)
+        def key(n):
+            p = self._params[n]
+            sub = len(GLITCH_DECLARED)
+            if p.component == "Glitch" and p.index == 1:
+                sub = GLITCH_DECLARED.index(n[:n.index("_") + 1])
+            return ranks[p.component], sub
+        return sorted(self._params, key=key)
 
     def as_parfile(self, include_info: bool = True, comment: str = None) -> str:
         """The model as par-file text (timing_model.py:2747 as_parfile, format "pint")."""
@@ -202,6 +222,21 @@ class TimingModel:
     def fd_terms(self) -> List[str]:
         return self.prefix_list(r"^FD(\d+)$")
 
+    def glitch_indices(self) -> List[int]:
+        """The glitch indices that appear in any GL*_n parameter, ascending (glitch.py:139-145)."""
+        return self._names_of("glitch", lambda: sorted({p.index for p in self._params.values()
+                                                        if p.component == "Glitch"}))
+
+    def setup_glitches(self):
+        """Glitch.setup (glitch.py:127-153): every glitch index that appears gets all seven
+        parameters, the missing ones 0 and frozen.  A missing epoch stays missing (validate)."""
+        for idx in self.glitch_indices():
+            for pre in GLITCH_PROPS:
+                if pre != "GLEP_" and f"{pre}{idx}" not in self._params:
+                    p = P.make_param(f"{pre}{idx}")
+                    p.value = 0.0
+                    self.add_param(p)
+
     def mask_params(self, base: str) -> List[str]:
         def build():
             rx = re.compile(rf"^{base}\d+$")
@@ -232,6 +267,17 @@ class TimingModel:
                                       "hot path (SWM 0 only)")
         if "CORRECT_TROPOSPHERE" in self and self.CORRECT_TROPOSPHERE.value:
             raise NotImplementedError("troposphere delay (CORRECT_TROPOSPHERE Y) is outside the supported hot path")
+        for idx in self.glitch_indices():  # Glitch.validate (glitch.py:155-183)
+            ep = self._params.get(f"GLEP_{idx}")
+            if ep is None or ep.value is None:
+                raise MissingParameter(f"Glitch GLEP_{idx}: Glitch Epoch is needed for Glitch {idx}.")
+            ph = self._params.get(f"GLPH_{idx}")
+            if ph is not None and not ep.frozen and not ph.frozen:
+                raise ValueError(f"Both the glitch epoch and phase cannot be fit for Glitch {idx}.")
+            f0d, td = self._params.get(f"GLF0D_{idx}"), self._params.get(f"GLTD_{idx}")
+            if f0d is not None and f0d.value and not (td is not None and td.value):
+                raise MissingParameter(f"Glitch GLTD_{idx}: None zero GLF0D_{idx} parameter needs a none zero "
+                                       f"GLTD_{idx} parameter")
         if self.binary in ("DD", "BT", "DDK"):
             e = float(self.ECC.value or 0.0)
             if not (0 <= e < 1):
@@ -452,6 +498,7 @@ def get_model(parfile) -> TimingModel:
                     p.set_uncertainty_from_string(l.fields[2])
             else:
                 p.set_uncertainty_from_string(fl)
+    model.setup_glitches()
     # components present
     comps = set()
     for n, p in model._params.items():
