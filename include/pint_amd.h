@@ -42,6 +42,8 @@ extern "C" {
 #define PINT_MAX_FD 10
 #define PINT_MAX_JUMP 64
 #define PINT_MAX_GLITCH 64    /* glitches per model (the JUMP cap; J0537-6910 has more than 32) */
+#define PINT_MAX_WAVEX 128    /* WaveX harmonics, and DMWaveX harmonics, per model (wavex_setup par files
+                                 carry 10-45 per component)                                          */
 
 /* ---- per-TOA packed input (reference TOAs.table columns
  *      toa.py:2320 tdbld, :2385-2439 posvels, freq, error, mjd_float, pulse_number) ---- */
@@ -105,9 +107,15 @@ enum {
     PINT_COL_ZERO = 12,     /* a parameter without a delay (DMJUMP, dispersion_model.py:797) */
     PINT_COL_NESW = 13,     /* NE_SW: d_delay_d_ne_sw = DMconst * solar_wind_geometry / bfreq^2
                                (solar_wind_dispersion.py:404-412), d_dm_d_ne_sw = the geometry (:394) */
-    PINT_COL_GLITCH = 14    /* a Glitch parameter: col_index = 7 * glitch + PINT_GL_*; -d_phase_d_p / F0
+    PINT_COL_GLITCH = 14,   /* a Glitch parameter: col_index = 7 * glitch + PINT_GL_*; -d_phase_d_p / F0
                                on the TOAs the glitch acts on, 0 elsewhere (glitch.py:234-344); a timing
                                column like any other (its wideband DM rows are zero)                 */
+    PINT_COL_WX = 15,       /* WXSIN_ / WXCOS_: col_index = 2 k + (0 sin, 1 cos), k the harmonic's position
+                               in ascending index; d_delay_d_p = sin / cos (2 pi WXFREQ_k (tdb - WXEPOCH)),
+                               the accumulated delay NOT subtracted (wavex.py:382-396); col_toff the
+                               amplitude's table slot                                                */
+    PINT_COL_DMWX = 16      /* DMWXSIN_ / DMWXCOS_: the same indexing; d_dm_d_p = sin / cos (2 pi
+                               DMWXFREQ_k (tdb - DMWXEPOCH)), times DMconst / bfreq^2 (dmwavex.py:373-387) */
 };
 /* the parameters of one glitch, in the order of its 7 table slots (glitch.py:130-138 glitch_prop) */
 enum {
@@ -216,6 +224,22 @@ int pint_add_pulsar(pint_ctx *ctx, const pint_toas_t *toas, const pint_spec_t *s
 /* pint_add_pulsar from the TOA table's columns (pint_pack_toas into the context's scratch). */
 int pint_add_pulsar_cols(pint_ctx *ctx, const pint_toa_cols_t *cols, const pint_spec_t *spec,
                          const double *red_freq, const double *red_phi);
+/* WaveX / DMWaveX (wavex.py, dmwavex.py) of pulsar `psr`: the Fourier-series delay components,
+ * described beside the spec (pint_spec_t keeps its layout).  Each component has one table block
+ * of its harmonics in ascending index, three dd pairs per harmonic -- FREQ (1/d), SIN, COS (s;
+ * pc cm^-3 for DMWaveX) -- at o_wx / o_dmwx (table slots, -1 for none), nwx / ndmwx harmonics
+ * (<= PINT_MAX_WAVEX), and its epoch (WXEPOCH / DMWXEPOCH, MJD) in the dd pair just before the
+ * block, at o - 2.  Both delays follow the binary's (timing_model.py DEFAULT_ORDER; dmwavex
+ * sorts after everything), on every evaluation row, the TZR row included:
+ *   WaveX    sum_k WXSIN_k sin a_k + WXCOS_k cos a_k, a_k = 2 pi WXFREQ_k (tdb - WXEPOCH - D),
+ *            D the delay accumulated before it in days (wavex.py:365-380);
+ *   DMWaveX  DMconst / bfreq^2 times sum_k DMWXSIN_k sin a'_k + DMWXCOS_k cos a'_k,
+ *            a'_k = 2 pi DMWXFREQ_k (tdb - DMWXEPOCH) (dmwavex.py:355-371).
+ * They run as a kernel of their own (k_wavex) after the evaluation and before the glitch
+ * kernel; a batch with either component runs its residual pass unfused.  Call after
+ * pint_add_pulsar* and before the first pint_set_instances that uses the pulsar; a model with
+ * neither component makes no call. */
+int pint_set_wavex(pint_ctx *ctx, int psr, int o_wx, int nwx, int o_dmwx, int ndmwx);
 
 /* Bind `ninst` instances (grid points, PTA pulsars, trial states): inst_psr[k] is a
  * pulsar id; `tables` concatenates each instance's parameter table (spec.tstride doubles,

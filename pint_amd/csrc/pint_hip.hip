@@ -110,6 +110,9 @@ struct PsrDev {
     int vb;  // k_gram_v binned DMX x Fourier tile (VB) for this pulsar
     double logsig;  // sum_i log sigma_i (s): the WLS likelihood normalisation (residuals.py:665)
     double sumw;    // sum_i 1/sigma_i^2 (s^-2)
+    // WaveX / DMWaveX (pint_set_wavex): table slot of each component's block of harmonics
+    // (FREQ, SIN, COS dd pairs, ascending index; the epoch's pair at o - 2) and their counts
+    int o_wx, nwx, o_dmwx, ndmwx;
 };
 
 struct InstDev {
@@ -639,6 +642,139 @@ __global__ __launch_bounds__(256) void k_sw_geom(const PsrDev* __restrict__ psrs
     const int r = blockIdx.y * 256 + threadIdx.x;
     if (r > I.n) return;
     swg[I.roff + r] = sw_geometry_row(Pd, ic[blockIdx.x], r);
+}
+
+// k_wavex: the WaveX and DMWaveX components (wavex.py:365-396, dmwavex.py:355-387) of the
+// instances whose model has either, after the evaluation and before k_glitch (whose dt takes
+// the total delay), on the evaluation's outputs.  Both delays follow the binary's in the
+// reference's sum and need nothing the evaluation keeps in registers, so like the glitch they
+// are a pass of their own and no k_eval* build changes.  Per evaluation row (TOAs and the TZR
+// row) the kernel adds the WaveX delay, evaluated at the evaluation's delay D, and the DMWaveX
+// delay, writes the total delay back, moves the spindown phase to it, and with Mout writes the
+// free PINT_COL_WX / PINT_COL_DMWX columns (the evaluation has zeroed them) in the full or the
+// compact fit layout.  One thread per row; grid (instances, row blocks of the longest
+// instance); the harmonic loops read the instance's table at block-uniform addresses; one
+// sincospi per harmonic serves the delay and the harmonic's two columns.
+//
+// sin and cos of a harmonic: the argument in half turns, x = 2 f (tdb - epoch), is formed in dd
+// (the epoch difference is exact there, the product by f carries 106 bits), reduced by its
+// nearest even integer (exact) and given to sincospi: no large-argument reduction at |a| of
+// thousands of radians, and an argument error of ~1e-17 half turns where a double product
+// would carry 2^-53 |x|.  That is a'_k, the partials' argument; s and c return its sine and
+// cosine.  The WaveX delay's own argument (ROT) is a_k = a'_k - e, e = 2 pi f D, D the delay
+// accumulated before it (wavex.py:372, `shift` in days): sin a and cos a come from sin a' and
+// cos a' by a rotation through e instead of a second full evaluation.  |e| <= 1/16 (f up to
+// 0.8 / d at a 1000 s delay) takes the series of sin e through e^7 and of cos e through e^8, whose
+// truncation is below e^9 / 9! = 4e-17 and e^10 / 10! = 3e-19 -- under an ulp of the unit-size
+// results, 1e-22 s on a microsecond amplitude; a larger e takes sincos.  Returns the harmonic's
+// delay term SIN_k sin a_k + COS_k cos a_k.
+template <bool ROT>
+__device__ __forceinline__ double wavex_harmonic(const double* H, dd dt_days, double shift, double& s, double& c) {
+    const double f2 = 2.0 * pval(H, 0);
+    const dd x = dd_mul_d(dt_days, f2);
+    const double n = 2.0 * rint(0.5 * x.hi);  // (a whole number of turns: sinpi has period 2)
+    sincospi((x.hi - n) + x.lo, &s, &c);
+    double sa = s, ca = c;
+    if (ROT) {
+        const double e = PI_D * f2 * shift, e2 = e * e;
+        double se, ce;
+        if (fabs(e) <= 0.0625) {
+            se = e * (1.0 - e2 * (1.0 / 6.0) * (1.0 - e2 * (1.0 / 20.0) * (1.0 - e2 * (1.0 / 42.0))));
+            ce = 1.0 - e2 * 0.5 * (1.0 - e2 * (1.0 / 12.0) * (1.0 - e2 * (1.0 / 30.0) * (1.0 - e2 * (1.0 / 56.0))));
+        } else {
+            sincos(e, &se, &ce);
+        }
+        sa = s * ce - c * se;
+        ca = c * ce + s * se;
+    }
+    return pval(H, 2) * sa + pval(H, 4) * ca;
+}
+// One component at row r: sum_k SIN_k sin a_k + COS_k cos a_k over its block B (3 dd pairs per
+// harmonic, ascending index -- one order of summation whatever is free, so a frozen amplitude
+// delays by the same bits), and with Mb the free columns of kind `kind`, scale * (sin | cos) a'_k,
+// from the same sincospi (Mb, ld, runs, compact as in eval_spin_b; wr: this row has a
+// design-matrix row).  A run's columns have consecutive indices 2 k + (0 sin, 1 cos); the kind's
+// runs are adjacent (its columns are), so each harmonic scans only those, at wave-uniform
+// addresses.
+template <bool ROT>
+__device__ __forceinline__ double wavex_component(const double* B, int nh, dd dt_days, double shift, int kind,
+                                                  double scale, double* Mb, bool wr, unsigned r, long ld,
+                                                  const ColRun* runs, int nrun, bool compact) {
+    int u0 = 0, u1 = 0;
+    if (Mb) {
+        u0 = nrun;
+        for (int u = 0; u < nrun; u++)
+            if (runs[u].kind == kind) {
+                u0 = u < u0 ? u : u0;
+                u1 = u + 1;
+            }
+    }
+    double v = 0.0;
+    for (int k = 0; k < nh; k++) {
+        double s, c;
+        v += wavex_harmonic<ROT>(B + 6 * k, dt_days, shift, s, c);
+        for (int u = u0; u < u1; u++) {
+            const ColRun R = runs[u];
+            if (R.kind != kind) continue;
+            const long col = compact ? R.dcol0 : R.col0;
+            const int js = 2 * k - R.idx0, jc = js + 1;
+            if (wr && js >= 0 && js < R.cnt) Mb[(col + js) * ld + r] = scale * s;
+            if (wr && jc >= 0 && jc < R.cnt) Mb[(col + jc) * ld + r] = scale * c;
+        }
+    }
+    return v;
+}
+__global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
+                                               const double* __restrict__ tables, const InstConst* __restrict__ ic,
+                                               double* __restrict__ delay, double* __restrict__ ph_hi,
+                                               double* __restrict__ ph_lo, double* __restrict__ Mout, int compact) {
+    const InstDev I = insts[blockIdx.x];
+    const PsrDev& Pd = psrs[I.psr];
+    const int nwx = Pd.nwx, ndmwx = Pd.ndmwx;
+    if (nwx + ndmwx <= 0) return;  // (block-uniform)
+    const int r = blockIdx.y * 256 + threadIdx.x;
+    if (r > I.n) return;
+    const pint_spec_t& S = *Pd.spec;
+    const double* P = tables + I.toff;
+    const InstConst& C = ic[blockIdx.x];
+    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
+    const double D = delay[I.roff + r];
+    // the spin frequency at the evaluation's dt (its delay D): d_phase_d_delay = -F(dt), so the
+    // columns are M = -(d_phase_d_delay d_delay_d_p) / F0 = chain d_delay_d_p, the chain factor
+    // of the other delay columns (F'(dt) d / F0 ~ 1e-22 apart at the new delay)
+    const double dtd = dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(P, S.o_PEPOCH)), DAYSEC), -D));
+    const double fdt = spin_freq(S, P, dtd);
+    const double chain = fdt * C.iF0;
+    double* Mb = Mout ? Mout + I.moff : nullptr;
+    const bool wr = r < I.n, cmp = compact && Pd.dsplit;
+    double wx = 0.0, dmd = 0.0;
+    if (nwx > 0)  // wavex_delay (wavex.py:365-380): the argument at tdb - WXEPOCH - D; the partials without D
+        wx = wavex_component<true>(P + Pd.o_wx, nwx, dd_sub(tdb, pdd(P, Pd.o_wx - 2)), D * (1.0 / DAYSEC), PINT_COL_WX,
+                                   chain, Mb, wr, (unsigned)r, I.n, Pd.runs, Pd.nrun, cmp);
+    if (ndmwx > 0) {  // dmwavex_dm (dmwavex.py:355-368) * DMconst / bfreq^2 (dispersion_type_delay)
+        // the barycentric radio frequency, as eval_pre forms it (astrometry.py:359-364): the
+        // evaluation keeps 1 / bfreq^2 per row only on the shared-head path
+        double bfreq = Pd.freq[r];
+        if (S.astrometry) {
+            double L[3];
+            psr_dir_icrs(C, dd_to_d(tdb), L);
+            const double vdl = Pd.vel[3 * r] * L[0] + Pd.vel[3 * r + 1] * L[1] + Pd.vel[3 * r + 2] * L[2];
+            bfreq *= 1.0 - vdl * INV_C_KMS;
+        }
+        const double dmscale = DMCONST / (bfreq * bfreq);
+        dmd = wavex_component<false>(P + Pd.o_dmwx, ndmwx, dd_sub(tdb, pdd(P, Pd.o_dmwx - 2)), 0.0, PINT_COL_DMWX,
+                                     chain * dmscale, Mb, wr, (unsigned)r, I.n, Pd.runs, Pd.nrun, cmp) * dmscale;
+    }
+    delay[I.roff + r] = (D + wx) + dmd;  // (the reference's order: ... binary, wavex, dmwavex)
+    // The spindown phase at the new total delay: phase(dt - d) = phase(dt) - d F(dt) + d^2 F'(dt) / 2
+    // - ..., d = wx + dmd, dt the evaluation's.  The first-order term is kept, as an exact product
+    // added in dd; the first dropped term, d^2 |F'(dt)| / 2, is 5e-16 cycle at d = 1 ms and
+    // |F1| = 1e-9 Hz/s (F0 <= 1 kHz enters the kept term only: d F <= 1 cycle, whose rounding in dd
+    // is below 1e-30) -- six orders below the 1e-10 s x F0 phase bar; d itself is tens of
+    // microseconds.
+    const dd ph = dd_sub(dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]), two_prod(wx + dmd, fdt));
+    ph_hi[I.roff + r] = ph.hi;
+    ph_lo[I.roff + r] = ph.lo;
 }
 
 // k_glitch: the Glitch component (glitch.py:193-344) of the instances whose model has glitches,
@@ -5658,6 +5794,7 @@ struct pint_ctx {
     double* d_epart = nullptr;    // fused residual pass (efz): per evaluation block sum w, sum w x
     int efz = 0;                  // the batch's evaluation blocks carry k_resid1 (EF_ROWS rows + row 0 + TZR)
     bool any_glitch = false;      // an instance's model has glitches: k_glitch follows the evaluation
+    bool any_wavex = false;       // ... has WaveX or DMWaveX: k_wavex follows the evaluation (before k_glitch)
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
@@ -6590,6 +6727,7 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
     ph.K = K;
     PsrDev& d = ph.dev;
     memset(&d, 0, sizeof(d));
+    d.o_wx = d.o_dmwx = -1;  // (pint_set_wavex)
     int rc = 0;
     rc |= stg(t->tdb_hi, n + 1, d.tdb_hi);
     rc |= stg(t->tdb_lo, n + 1, d.tdb_lo);
@@ -6736,6 +6874,25 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
     if (trig_setup) ctx->setup_pending.push_back((int)ctx->psrs.size() - 1);
     ctx->psrs_dirty = true;  // the device descriptor array is rebuilt once, at pint_set_instances
     return (int)ctx->psrs.size() - 1;
+}
+
+int pint_set_wavex(pint_ctx* ctx, int psr, int o_wx, int nwx, int o_dmwx, int ndmwx) {
+    if (!ctx || psr < 0 || psr >= (int)ctx->psrs.size()) return PINT_E_INVALID;
+    PsrHost& ph = ctx->psrs[psr];
+    // each block: its epoch's dd pair at o - 2, then 3 dd pairs per harmonic, inside the table
+    auto bad = [&](int o, int n) {
+        return n < 0 || n > PINT_MAX_WAVEX || (n > 0 && (o < 2 || (long)o + 6L * n > (long)ph.spec.tstride));
+    };
+    if (bad(o_wx, nwx) || bad(o_dmwx, ndmwx)) {
+        ctx->err = "bad WaveX / DMWaveX block or harmonic count (PINT_MAX_WAVEX)";
+        return PINT_E_INVALID;
+    }
+    ph.dev.o_wx = nwx > 0 ? o_wx : -1;
+    ph.dev.nwx = nwx;
+    ph.dev.o_dmwx = ndmwx > 0 ? o_dmwx : -1;
+    ph.dev.ndmwx = ndmwx;
+    ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
+    return PINT_OK;
 }
 
 int pint_fit_layout(pint_ctx* ctx, int psr, int32_t* out4) {
@@ -6956,7 +7113,13 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     // (not for a batch with glitches: their phase is added after the evaluation, by k_glitch)
     ctx->any_glitch = false;
     for (int k = 0; k < ninst; k++) ctx->any_glitch = ctx->any_glitch || ctx->psrs[inst_psr[k]].spec.nglitch > 0;
-    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch;
+    // (nor with WaveX / DMWaveX: k_wavex moves the delay and the phase after the evaluation)
+    ctx->any_wavex = false;
+    for (int k = 0; k < ninst; k++) {
+        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
+        ctx->any_wavex = ctx->any_wavex || d.nwx + d.ndmwx > 0;
+    }
+    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch && !ctx->any_wavex;
     long ebn = 0;
     // N-split for the Gram so the launch fills the 256 CUs
     // choose the split count that minimises (workgroup rounds) / nsplit, i.e. the k_gram
@@ -7705,6 +7868,12 @@ int pint_eval(pint_ctx* ctx, int want_M) {
 #undef PINT_EVAL_LAUNCH
         HIPCHK(hipGetLastError());
     }
+    if (ctx->any_wavex) {  // WaveX / DMWaveX: the total delay, the phase at it and their columns (before k_glitch)
+        hipLaunchKernelGGL(k_wavex, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
+                           want_M == 2 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
     if (ctx->any_glitch) {  // Glitch: the phase of every row and the glitch columns, on the evaluation's outputs
         hipLaunchKernelGGL(k_glitch, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
@@ -7774,6 +7943,10 @@ int pint_set_wideband(pint_ctx* ctx, int psr, const double* pp_dm, const double*
     if (int rc_ = commit_uploads(ctx)) return rc_;  // (staged pulsar uploads first)
     PsrHost& ph = ctx->psrs[psr];
     if (ph.spec.ndmjump > 0 && !dmjump_mask) { ctx->err = "DMJUMPs without masks"; return PINT_E_INVALID; }
+    if (ph.dev.nwx + ph.dev.ndmwx > 0) {  // (DMWaveX's share of the modelled DM and of the DM rows is not formed)
+        ctx->err = "wideband DM data with WaveX / DMWaveX is not supported";
+        return PINT_E_INVALID;
+    }
     for (int i = 0; i < ph.n; i++)
         if (!(dm_sigma[i] > 0.0) || !(pp_dme[i] > 0.0)) {
             ctx->err = "Some DM errors are zero - cannot calculate the weighted residuals.";

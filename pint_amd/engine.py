@@ -52,6 +52,8 @@ class PulsarLayout:
     ep_idx: Optional[np.ndarray] = None
     ep_phi: Optional[np.ndarray] = None
     ep_param: Optional[list] = None  # the ECORR parameter of each epoch
+    # WaveX / DMWaveX (pint_set_wavex): (o_wx, nwx, o_dmwx, ndmwx), None for a model with neither
+    wavex: Optional[tuple] = None
 
 
 def _track_mode(model, toas, track_mode):
@@ -165,6 +167,24 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
             for w, pre in enumerate(GLITCH_PROPS):
                 place(f"{pre}{idx}")
                 glitch_cols[f"{pre}{idx}"] = (L.COL_GLITCH, L.GL_NPAR * k + w)
+    # WaveX / DMWaveX: per component the epoch's slot, then one block of (FREQ, SIN, COS) slots per
+    # harmonic in ascending index; described to the library beside the spec (pint_set_wavex), so
+    # a model with neither keeps its spec, table and offsets
+    wx_desc, wx_cols = [], {}
+    for comp, pre, kind in (("WaveX", "WX", L.COL_WX), ("DMWaveX", "DMWX", L.COL_DMWX)):
+        idxs = model.wavex_indices(comp)
+        if len(idxs) > L.MAX_WAVEX:
+            raise NotImplementedError(f"more than {L.MAX_WAVEX} {comp} harmonics (PINT_MAX_WAVEX)")
+        if not idxs:
+            wx_desc += [-1, 0]
+            continue
+        place(f"{pre}EPOCH")
+        wx_desc += [pos, len(idxs)]
+        for k, idx in enumerate(idxs):
+            place(f"{pre}FREQ_{idx:04d}")
+            for w, part in enumerate(("SIN", "COS")):
+                place(f"{pre}{part}_{idx:04d}")
+                wx_cols[f"{pre}{part}_{idx:04d}"] = (kind, 2 * k + w)
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
                    "DDK": L.BIN_DDK}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
@@ -214,6 +234,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         for nm in names:
             kind_of[nm] = (kk, 0)
     kind_of.update(glitch_cols)
+    kind_of.update(wx_cols)
     # (later groups first, so that an earlier group wins a shared name, as the if-chain did)
     for group, kk in ((dmjumps, L.COL_ZERO), (jumps, L.COL_JUMP), (fds, L.COL_FD), (dmx, L.COL_DMX),
                       (dms, L.COL_DM), (F, L.COL_F)):
@@ -271,6 +292,8 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
     spec.dmn0 = dmn0 if (use_gls_basis and "PLDMNoise" in model.components) else nred
     lay = PulsarLayout(model=model, toas=toas, n=toas.ntoas, offsets=offs, tstride=tstride, columns=cols,
                        spec=spec, nred=nred, K=len(cols) + 2 * nred, red_freq=rf, red_phi=rp, track_mode=tm)
+    if wx_cols:
+        lay.wavex = tuple(wx_desc)
     if ep_lists:
         lay.nep = len(ep_lists)
         lay.ep_ptr = np.concatenate([[0], np.cumsum([len(e) for e in ep_lists])]).astype(np.int32)
@@ -617,6 +640,8 @@ class Session:
         if lay.nep > 0:
             self._check(self.L.pint_set_ecorr(self.ctx, pid, lay.nep, L.ptr(lay.ep_ptr, C.c_int32),
                                               L.ptr(lay.ep_idx, C.c_int32), L.ptr(lay.ep_phi)))
+        if lay.wavex is not None:
+            self._check(self.L.pint_set_wavex(self.ctx, pid, *lay.wavex))
         self.layouts.append(lay)
         return lay
 

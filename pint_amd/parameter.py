@@ -170,6 +170,9 @@ _DEFS = {
     "CORRECT_TROPOSPHERE": ("TroposphereDelay", "bool", "", False, None),
     "NE_SW": ("SolarWindDispersion", "float", "1 / cm3", False, None),
     "SWM": ("SolarWindDispersion", "int", "", False, None),
+    # WaveX / DMWaveX epochs (wavex.py:51-58, dmwavex.py)
+    "WXEPOCH": ("WaveX", "mjd", "d", True, None),
+    "DMWXEPOCH": ("DMWaveX", "mjd", "d", True, None),
     # binaries (pulsar_binary.py, binary_ell1.py, binary_dd.py)
     "PB": ("Binary", "float", "d", True, None),
     "PBDOT": ("Binary", "float", "", False, (1e-12, 1e-7)),
@@ -225,6 +228,14 @@ _PREFIX = {  # prefix params: regex -> (component, units template, long_double)
     r"^GLF2_(\d+)$": ("Glitch", "Hz / s2", False),
     r"^GLF0D_(\d+)$": ("Glitch", "Hz", False),
     r"^GLTD_(\d+)$": ("Glitch", "d", False),
+    # WaveX (wavex.py:105-136) and DMWaveX (dmwavex.py): float64; only the four-digit index is a
+    # par-file name (the reference does not recognise WXSIN_1)
+    r"^WXFREQ_(\d{4})$": ("WaveX", "1 / d", False),
+    r"^WXSIN_(\d{4})$": ("WaveX", "s", False),
+    r"^WXCOS_(\d{4})$": ("WaveX", "s", False),
+    r"^DMWXFREQ_(\d{4})$": ("DMWaveX", "1 / d", False),
+    r"^DMWXSIN_(\d{4})$": ("DMWaveX", "pc / cm3", False),
+    r"^DMWXCOS_(\d{4})$": ("DMWaveX", "pc / cm3", False),
 }
 
 MASK_PARAMS = {"JUMP": ("PhaseJump", "s"), "EFAC": ("ScaleToaError", ""),
@@ -250,7 +261,7 @@ def make_param(name: str) -> Optional[Param]:
             u = units.replace("{n}", str(idx))
             if name == "F0":
                 u = "Hz"
-            if name.startswith("DM") and not name.startswith("DMX") and idx == 0:
+            if name.startswith("DM") and not name.startswith(("DMX", "DMWX")) and idx == 0:
                 return None
             return Param(name=name, kind=kind, units=u, long_double=ld, component=comp, index=idx)
     return None

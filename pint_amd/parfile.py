@@ -30,6 +30,9 @@ NE_SW (fit flag and uncertainty like any fitted parameter) and SWM as the refere
 ``print_par`` does (``solar_wind_dispersion.py:453-459``; SWP belongs to SWM 1 only).
 A model with glitches writes, per glitch in ascending index, GLEP_ GLPH_ GLF0_ GLF1_ GLF2_
 GLF0D_ GLTD_, the ones ``setup`` filled in with 0 included (``glitch.py:185-191``).
+A model with WaveX or DMWaveX writes the component's epoch, then ``FREQ_ SIN_ COS_`` of each
+harmonic in parameter order (harmonic 0001, which the component always has, first), after the
+binary's lines; a frequency line carries no fit flag.
 """
 from __future__ import annotations
 
@@ -244,8 +247,8 @@ _ORDER = {
     "PLDMNoise": ["TNDMAMP", "TNDMGAM", "TNDMC"],
 }
 MIDDLE = ["TroposphereDelay", "SolarSystemShapiro", "SolarWindDispersion", "DispersionDM", "DispersionDMX",
-          "Binary", "FD", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise", "ScaleToaError",
-          "PLRedNoise", "PLDMNoise"]
+          "Binary", "FD", "WaveX", "DMWaveX", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise",
+          "ScaleToaError", "PLRedNoise", "PLDMNoise"]
 
 
 def _by_index(names, prefix):

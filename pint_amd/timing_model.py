@@ -21,7 +21,8 @@ from .parameter import LD, Param
 
 # components supported on the hot path
 DELAY_ORDER = ["AstrometryEquatorial", "AstrometryEcliptic", "TroposphereDelay", "SolarSystemShapiro",
-               "SolarWindDispersion", "DispersionDM", "DispersionDMX", "BinaryELL1", "BinaryDD", "FD"]
+               "SolarWindDispersion", "DispersionDM", "DispersionDMX", "BinaryELL1", "BinaryDD", "FD", "WaveX",
+               "DMWaveX"]
 PHASE_ORDER = ["AbsPhase", "Spindown", "Glitch", "PhaseOffset", "PhaseJump"]
 NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
 
@@ -30,6 +31,11 @@ NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
 # PINT_GL_*; and the order the component declares its index-1 parameters in (:56-124)
 GLITCH_PROPS = ("GLEP_", "GLPH_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_")
 GLITCH_DECLARED = ("GLPH_", "GLEP_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_")
+
+# WaveX / DMWaveX (wavex.py, dmwavex.py): component -> parameter-name stem.  wavex is the last
+# category of the reference's DEFAULT_ORDER and dmwavex is not in it (it sorts after everything,
+# timing_model.py:1296): both delays follow the binary's, and their parameters follow its.
+WAVEX_STEMS = {"WaveX": "WX", "DMWaveX": "DMWX"}
 
 ELL1_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "EDOT", "OMDOT", "M2", "SINI", "TASC", "EPS1", "EPS2",
                "EPS1DOT", "EPS2DOT"]
@@ -79,6 +85,13 @@ class TimingModel:
     def add_param(self, p: Param):
         self._params[p.name] = p
         self.components.setdefault(p.component or "TimingModel", []).append(p.name)
+        object.__setattr__(self, "_order", None)
+        object.__setattr__(self, "_names", {})
+
+    def remove_param(self, name: str):
+        """Component.remove_param (timing_model.py): the caches keyed on the parameter count go too."""
+        p = self._params.pop(name)
+        self.components[p.component or "TimingModel"].remove(name)
         object.__setattr__(self, "_order", None)
         object.__setattr__(self, "_names", {})
 
@@ -237,6 +250,111 @@ class TimingModel:
                     p.value = 0.0
                     self.add_param(p)
 
+    # -- WaveX / DMWaveX (wavex.py:63-289, dmwavex.py) ------------------------------------------
+    def _wavex_map(self, comp: str, part: str) -> Dict[int, str]:
+        """get_prefix_mapping_component(f"{stem}{part}_"): {index: name} in parameter order."""
+        pre = f"{WAVEX_STEMS[comp]}{part}_"
+        return {p.index: n for n, p in self._params.items() if p.component == comp and n.startswith(pre)}
+
+    def wavex_indices(self, comp: str = "WaveX") -> List[int]:
+        """The component's harmonic indices, ascending: the order of its table block and of
+        col_index."""
+        return sorted(self._wavex_map(comp, "FREQ")) if comp in self.components else []
+
+    def get_wavex_indices(self, component: str = "WaveX"):
+        """WaveX.get_indices (wavex.py:279-289): the indices of the FREQ parameters, in
+        parameter order."""
+        return np.array(list(self._wavex_map(component, "FREQ")), dtype=int)
+
+    def _ensure_wavex(self, comp: str):
+        """The component as its constructor leaves it (wavex.py:49-60): the epoch unset, and
+        harmonic 0001 at 0.1 / d with zero, *free* amplitudes."""
+        stem = WAVEX_STEMS[comp]
+        for name, value, frozen in ((f"{stem}EPOCH", None, True), (f"{stem}FREQ_0001", 0.1, True),
+                                    (f"{stem}SIN_0001", 0.0, False), (f"{stem}COS_0001", 0.0, False)):
+            if name not in self._params:
+                p = P.make_param(name)
+                p.value, p.frozen = value, frozen
+                self.add_param(p)
+
+    def add_wavex_component(self, wxfreq, index=None, wxsin=0, wxcos=0, frozen=True, component="WaveX"):
+        """WaveX.add_wavex_component (wavex.py:63-139); returns the index given to the harmonic."""
+        return self.add_wavex_components([wxfreq], None if index is None else [index], wxsin, wxcos, frozen,
+                                         component=component)[0]
+
+    def add_wavex_components(self, wxfreqs, indices=None, wxsins=0, wxcoses=0, frozens=True, component="WaveX"):
+        """WaveX.add_wavex_components (wavex.py:141-253): harmonics at the given frequencies
+        (1 / d), amplitudes in s (pc / cm3 for DMWaveX); an index of None takes the largest
+        index in use plus one.  Returns the indices."""
+        stem = WAVEX_STEMS[component]
+        wxfreqs = [float(f) for f in np.atleast_1d(np.asarray(wxfreqs, dtype=np.float64))]
+        n = len(wxfreqs)
+        indices = [None] * n if indices is None else list(indices)
+        cols = []
+        for vals, what in ((wxsins, "sine ampltudes"), (wxcoses, "cosine ampltudes")):
+            vals = np.atleast_1d(vals)
+            if len(vals) == 1:
+                vals = np.repeat(vals, n)
+            if len(vals) != n:
+                raise ValueError(f"Number of base frequencies {n} doesn't match number of {what} {len(vals)}")
+            cols.append(vals)
+        frozens = np.atleast_1d(frozens)
+        if len(frozens) == 1:
+            frozens = np.repeat(frozens, n)
+        if len(frozens) != n:
+            raise ValueError("Number of base frequencies must match number of frozen values")
+        self._ensure_wavex(component)
+        used = self._wavex_map(component, "FREQ")
+        last = max(used)
+        added = []
+        for f, index, s_, c_, fr in zip(wxfreqs, indices, cols[0], cols[1], frozens):
+            if index is None:
+                index = last = last + 1
+            elif int(index) in used or int(index) in added:
+                raise ValueError(f"Index '{index}' is already in use in this model. Please choose another")
+            added.append(int(index))
+            for part, v, frz in (("FREQ", f, True), ("SIN", float(s_), bool(fr)), ("COS", float(c_), bool(fr))):
+                p = P.make_param(f"{stem}{part}_{int(index):04d}")
+                p.value, p.frozen = v, frz
+                self.add_param(p)
+        self.validate_wavex(component)
+        return added
+
+    def remove_wavex_component(self, index, component="WaveX"):
+        """WaveX.remove_wavex_component (wavex.py:255-277): an index or a list of indices."""
+        if isinstance(index, (int, float, np.integer)):
+            index = [index]
+        elif not isinstance(index, (list, set, np.ndarray)):
+            raise TypeError(f"index most be a float, int, set, list, or array - not {type(index)}")
+        stem = WAVEX_STEMS[component]
+        for i in index:
+            for part in ("FREQ", "SIN", "COS"):
+                self.remove_param(f"{stem}{part}_{int(i):04d}")
+        self.validate_wavex(component)
+
+    def validate_wavex(self, comp: str):
+        """WaveX.validate / DMWaveX.validate (wavex.py:303-360, dmwavex.py:293-350)."""
+        import warnings
+        if comp not in self.components:
+            return
+        stem = WAVEX_STEMS[comp]
+        fm, sm, cm = (self._wavex_map(comp, part) for part in ("FREQ", "SIN", "COS"))
+        for a, b, an, bn in ((fm, sm, "FREQ", "SIN"), (fm, cm, "FREQ", "COS"), (sm, cm, "SIN", "COS")):
+            if a.keys() != b.keys():
+                raise ValueError(f"{stem}{an}_ parameters do not match {stem}{bn}_ parameters."
+                                 "Please check your prefixed parameters")
+        for name in fm.values():
+            v = self._params[name].value
+            if v is None or v == 0:
+                raise ValueError(f"{name} is zero or None. Please check your prefixed parameters")
+            if v < 0.0:
+                warnings.warn(f"Frequency {name} is negative")
+        ep = self._params[f"{stem}EPOCH"]
+        if ep.value is None:
+            if "PEPOCH" not in self._params or self.PEPOCH.value is None:
+                raise MissingParameter(f"{stem}EPOCH or PEPOCH are required if {comp} is being used")
+            ep.value = LD(self.PEPOCH.value)
+
     def mask_params(self, base: str) -> List[str]:
         def build():
             rx = re.compile(rf"^{base}\d+$")
@@ -278,6 +396,8 @@ class TimingModel:
             if f0d is not None and f0d.value and not (td is not None and td.value):
                 raise MissingParameter(f"Glitch GLTD_{idx}: None zero GLF0D_{idx} parameter needs a none zero "
                                        f"GLTD_{idx} parameter")
+        for comp in WAVEX_STEMS:
+            self.validate_wavex(comp)
         if self.binary in ("DD", "BT", "DDK"):
             e = float(self.ECC.value or 0.0)
             if not (0 <= e < 1):
@@ -422,6 +542,7 @@ def get_model(parfile) -> TimingModel:
         defaults += [("SWM", 0)]
     if any(n == "DM" or re.match(r"^DM\d+$", n) for n in names):
         defaults += [("DM", LD(0)), ("DMEPOCH", None)]
+    wavex_rx = re.compile(r"^(DM)?WX(EPOCH|(FREQ|SIN|COS)_\d+)$")
     if binary in ("ELL1", "ELL1H"):
         defaults += [(n, 0.0) for n in ELL1_PARAMS if not (binary == "ELL1H" and n in ("M2", "SINI"))]
         defaults += [("TASC", None)]
@@ -450,6 +571,10 @@ def get_model(parfile) -> TimingModel:
         if p.component == "Binary":
             p.component = "Binary"
         model.add_param(p)
+    # WaveX, then DMWaveX, after the binary's parameters (the components as constructed)
+    for comp, stem in WAVEX_STEMS.items():
+        if any(re.match(rf"^{stem}(EPOCH|(FREQ|SIN|COS)_\d{{4}})$", n) for n in names):
+            model._ensure_wavex(comp)
     for l in lines:
         raw = l.name
         name = P._ALIASES.get(raw, raw)
@@ -471,6 +596,10 @@ def get_model(parfile) -> TimingModel:
             p = P.make_param(name)
             if p is None:
                 if name in ("FB0", "SWP", "H3", "STIGMA"):
+                    continue
+                if wavex_rx.match(name):  # (only the four-digit index is a name: model_builder warns and goes on)
+                    import warnings
+                    warnings.warn(f"Unrecognized parfile line '{' '.join([raw] + l.fields)}'")
                     continue
                 raise NotImplementedError(f"parameter {raw} is outside the supported hot path")
             model.add_param(p)
