@@ -43,7 +43,11 @@ extern "C" {
 #define PINT_MAX_JUMP 64
 #define PINT_MAX_GLITCH 64    /* glitches per model (the JUMP cap; J0537-6910 has more than 32) */
 #define PINT_MAX_WAVEX 128    /* WaveX harmonics, and DMWaveX harmonics, per model (wavex_setup par files
-                                 carry 10-45 per component)                                          */
+                                 carry 10-45 per component); CMWaveX harmonics too                   */
+#define PINT_MAX_CM 16        /* ChromaticCM Taylor terms CM, CM1, ... per model                        */
+#define PINT_MAX_ADDED_DELAY 1.0 /* s: the largest |WaveX + DMWaveX + ChromaticCM + CMWaveX| delay of a row
+                                 for which the phase moved to it holds 1e-12 cycle (k_wavex); a model
+                                 beyond it fails with PINT_E_PARAM                                     */
 
 /* ---- per-TOA packed input (reference TOAs.table columns
  *      toa.py:2320 tdbld, :2385-2439 posvels, freq, error, mjd_float, pulse_number) ---- */
@@ -114,8 +118,14 @@ enum {
                                in ascending index; d_delay_d_p = sin / cos (2 pi WXFREQ_k (tdb - WXEPOCH)),
                                the accumulated delay NOT subtracted (wavex.py:382-396); col_toff the
                                amplitude's table slot                                                */
-    PINT_COL_DMWX = 16      /* DMWXSIN_ / DMWXCOS_: the same indexing; d_dm_d_p = sin / cos (2 pi
+    PINT_COL_DMWX = 16,     /* DMWXSIN_ / DMWXCOS_: the same indexing; d_dm_d_p = sin / cos (2 pi
                                DMWXFREQ_k (tdb - DMWXEPOCH)), times DMconst / bfreq^2 (dmwavex.py:373-387) */
+    PINT_COL_CM = 17,       /* CM, CM1, ...: col_index = the Taylor order k; d_delay_d_p = DMconst
+                               bfreq^(-TNCHROMIDX) dt^k / k!, dt years since CMEPOCH
+                               (chromatic_model.py:64-90, :250-270)                                   */
+    PINT_COL_CMWX = 18      /* CMWXSIN_ / CMWXCOS_: col_index = 2 k + (0 sin, 1 cos); d_cm_d_p = sin / cos
+                               (2 pi CMWXFREQ_k (tdb - CMWXEPOCH)), times DMconst bfreq^(-TNCHROMIDX)
+                               (cmwavex.py:373-387)                                                   */
 };
 /* the parameters of one glitch, in the order of its 7 table slots (glitch.py:130-138 glitch_prop) */
 enum {
@@ -240,6 +250,20 @@ int pint_add_pulsar_cols(pint_ctx *ctx, const pint_toa_cols_t *cols, const pint_
  * pint_add_pulsar* and before the first pint_set_instances that uses the pulsar; a model with
  * neither component makes no call. */
 int pint_set_wavex(pint_ctx *ctx, int psr, int o_wx, int nwx, int o_dmwx, int ndmwx);
+/* ChromaticCM / CMWaveX (chromatic_model.py, cmwavex.py) of pulsar `psr`, described beside the
+ * spec like WaveX: delays DMconst bfreq^(-alpha) CM(t) with alpha = TNCHROMIDX, any real number.
+ *   ChromaticCM  ncm (1..PINT_MAX_CM) Taylor terms CM, CM1, ... (per yr^k) as dd pairs at table
+ *                slot o_cm, then CMEPOCH's pair (MJD; 0 when the model has none) and
+ *                TNCHROMIDX's pair: CM(t) = sum_k CMk dt^k / k!, dt years since CMEPOCH;
+ *   CMWaveX      ncmwx (<= PINT_MAX_WAVEX) harmonics in a block at o_cmwx laid out as a WaveX
+ *                block (FREQ, SIN, COS; CMWXEPOCH's pair at o_cmwx - 2): CM(t) = sum_k CMWXSIN_k
+ *                sin a'_k + CMWXCOS_k cos a'_k, a'_k = 2 pi CMWXFREQ_k (tdb - CMWXEPOCH).  Only
+ *                beside a ChromaticCM, whose TNCHROMIDX it uses.
+ * Both follow WaveX and DMWaveX in the delay sum, in this order, inside the same pass (the
+ * chromatic build of k_wavex); a batch without chromatic terms launches what it launched
+ * before.  The four delays of a row may sum to at most PINT_MAX_ADDED_DELAY.  Same calling
+ * rule as pint_set_wavex; a model with neither component makes no call. */
+int pint_set_chromatic(pint_ctx *ctx, int psr, int o_cm, int ncm, int o_cmwx, int ncmwx);
 
 /* Bind `ninst` instances (grid points, PTA pulsars, trial states): inst_psr[k] is a
  * pulsar id; `tables` concatenates each instance's parameter table (spec.tstride doubles,

@@ -13,6 +13,6 @@ from .fitter import (Fitter, WLSFitter, GLSFitter, DownhillWLSFitter, DownhillGL
                      WidebandDownhillFitter,  # noqa: F401
                      MaxiterReached, StepProblem, InvalidModelParameters, CorrelatedErrors)
 from .gridutils import grid_chisq, grid_chisq_derived, tuple_chisq, tuple_chisq_derived  # noqa: F401
-from .wavex import wavex_setup, dmwavex_setup, get_wavex_freqs, get_wavex_amps  # noqa: F401
+from .wavex import wavex_setup, dmwavex_setup, cmwavex_setup, get_wavex_freqs, get_wavex_amps  # noqa: F401
 
 __version__ = "0.1.0"

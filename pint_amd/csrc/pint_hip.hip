@@ -113,6 +113,9 @@ struct PsrDev {
     // WaveX / DMWaveX (pint_set_wavex): table slot of each component's block of harmonics
     // (FREQ, SIN, COS dd pairs, ascending index; the epoch's pair at o - 2) and their counts
     int o_wx, nwx, o_dmwx, ndmwx;
+    // ChromaticCM / CMWaveX (pint_set_chromatic): the CM Taylor terms' slot and count (CMEPOCH's pair
+    // at o_cm + 2 ncm, TNCHROMIDX's after it), the CMWaveX block like a WaveX block
+    int o_cm, ncm, o_cmwx, ncmwx;
 };
 
 struct InstDev {
@@ -724,14 +727,37 @@ __device__ __forceinline__ double wavex_component(const double* B, int nh, dd dt
     }
     return v;
 }
+//
+// CHROM: the build for a batch in which some model has chromatic terms (pint_set_chromatic):
+// ChromaticCM (chromatic_model.py:211-235) and CMWaveX (cmwavex.py:355-371) in the same pass, so
+// a row's delay and phase are read and written once and bfreq is formed once.  Per row
+//   X = DMconst * bfreq^(-alpha), alpha = TNCHROMIDX (a table value: any real, per instance),
+// one pow per row, reused by both delays and every column;
+//   ChromaticCM  X * (CM + dt (CM1 + dt / 2 (CM2 + ...))), dt = (tdb - CMEPOCH) / 365.25 d
+//                (taylor_horner; with every higher term zero the sum is CM whatever dt is),
+//                columns chain * X * dt^k / k!;
+//   CMWaveX      X * sum_j CMWXSIN_j sin a'_j + CMWXCOS_j cos a'_j, a'_j = 2 pi CMWXFREQ_j (tdb -
+//                CMWXEPOCH), no accumulated-delay shift (as DMWaveX), columns chain * X * (sin | cos) a'_j.
+// The reference's DelayComponent_list of a model with a binary and all four ends ... BinaryELL1,
+// WaveX, DMWaveX, ChromaticCM, CMWaveX in the run the fixtures were captured in: wavex is the last
+// category of DEFAULT_ORDER; dmwavex, chromatic_constant and cmwavex are not in it and follow in
+// the order the model builder added them, which is the iteration order of a set of names and so
+// changes with the interpreter's hash seed (all six orders of the three occur).  TimingModel.delay
+// adds the components in turn, so the total is ((((D + wavex) + dmwavex) + cm) + cmwavex): that
+// floating-point order is the one kept here (the others differ from it by an ulp of the total).  A pulsar
+// without chromatic terms in such a batch takes the same operations as in the plain build.  The
+// plain build (CHROM false) is the kernel as it was.
+template <bool CHROM>
 __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
                                                const double* __restrict__ tables, const InstConst* __restrict__ ic,
                                                double* __restrict__ delay, double* __restrict__ ph_hi,
-                                               double* __restrict__ ph_lo, double* __restrict__ Mout, int compact) {
+                                               double* __restrict__ ph_lo, double* __restrict__ Mout, int compact,
+                                               int* __restrict__ status, int* __restrict__ istatus) {
     const InstDev I = insts[blockIdx.x];
     const PsrDev& Pd = psrs[I.psr];
     const int nwx = Pd.nwx, ndmwx = Pd.ndmwx;
-    if (nwx + ndmwx <= 0) return;  // (block-uniform)
+    const int ncm = CHROM ? Pd.ncm : 0, ncmwx = CHROM ? Pd.ncmwx : 0;
+    if (nwx + ndmwx + ncm + ncmwx <= 0) return;  // (block-uniform)
     const int r = blockIdx.y * 256 + threadIdx.x;
     if (r > I.n) return;
     const pint_spec_t& S = *Pd.spec;
@@ -751,28 +777,87 @@ __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, 
     if (nwx > 0)  // wavex_delay (wavex.py:365-380): the argument at tdb - WXEPOCH - D; the partials without D
         wx = wavex_component<true>(P + Pd.o_wx, nwx, dd_sub(tdb, pdd(P, Pd.o_wx - 2)), D * (1.0 / DAYSEC), PINT_COL_WX,
                                    chain, Mb, wr, (unsigned)r, I.n, Pd.runs, Pd.nrun, cmp);
-    if (ndmwx > 0) {  // dmwavex_dm (dmwavex.py:355-368) * DMconst / bfreq^2 (dispersion_type_delay)
+    double bfreq = 0.0;
+    if (ndmwx > 0 || ncm + ncmwx > 0) {  // dmwavex_dm (dmwavex.py:355-368) * DMconst / bfreq^2 (dispersion_type_delay)
         // the barycentric radio frequency, as eval_pre forms it (astrometry.py:359-364): the
         // evaluation keeps 1 / bfreq^2 per row only on the shared-head path
-        double bfreq = Pd.freq[r];
+        bfreq = Pd.freq[r];
         if (S.astrometry) {
             double L[3];
             psr_dir_icrs(C, dd_to_d(tdb), L);
             const double vdl = Pd.vel[3 * r] * L[0] + Pd.vel[3 * r + 1] * L[1] + Pd.vel[3 * r + 2] * L[2];
             bfreq *= 1.0 - vdl * INV_C_KMS;
         }
+    }
+    if (ndmwx > 0) {
         const double dmscale = DMCONST / (bfreq * bfreq);
         dmd = wavex_component<false>(P + Pd.o_dmwx, ndmwx, dd_sub(tdb, pdd(P, Pd.o_dmwx - 2)), 0.0, PINT_COL_DMWX,
                                      chain * dmscale, Mb, wr, (unsigned)r, I.n, Pd.runs, Pd.nrun, cmp) * dmscale;
     }
-    delay[I.roff + r] = (D + wx) + dmd;  // (the reference's order: ... binary, wavex, dmwavex)
+    double tot = (D + wx) + dmd;  // (the reference's order: ... binary, wavex, dmwavex)
+    double dsum = wx + dmd;
+    if (CHROM && ncm + ncmwx > 0) {
+        // X = DMconst * bfreq^(-alpha) (chromatic_time_delay, chromatic_model.py:25-31): one pow per
+        // row, whatever alpha is; the alpha slot follows the CM terms and CMEPOCH
+        const double X = DMCONST * pow(bfreq, -pval(P, Pd.o_cm + 2 * ncm + 2));
+        // base_cm (chromatic_model.py:211-228): taylor_horner in years since CMEPOCH
+        const double dty = dd_to_d(dd_sub(tdb, pdd(P, Pd.o_cm + 2 * ncm))) * INV_DJY;
+        double cm = pval(P, Pd.o_cm + 2 * (ncm - 1));
+        for (int k = ncm - 1; k >= 1; k--) cm = cm * dty * inv_int(k) + pval(P, Pd.o_cm + 2 * (k - 1));
+        const double cmd = cm * X;
+        if (Mb && wr) {  // d_delay_d_cmparam (:64-90): DMconst * dt^k / k! * bfreq^(-alpha), times the chain factor
+            const double cx = chain * X;
+            for (int u = 0; u < Pd.nrun; u++) {
+                const ColRun R = Pd.runs[u];
+                if (R.kind != PINT_COL_CM) continue;
+                double* colp = Mb + (long)(cmp ? R.dcol0 : R.col0) * I.n;
+                double v = 1.0;
+                for (int j = 1; j <= R.idx0; j++) v = v * dty * inv_int(j);
+                for (int j = 0; j < R.cnt; j++, colp += I.n) {
+                    if (j > 0) v = v * dty * inv_int(R.idx0 + j);
+                    colp[r] = cx * v;
+                }
+            }
+        }
+        tot += cmd;
+        dsum += cmd;
+        if (ncmwx > 0) {  // cmwavex_cm (cmwavex.py:355-368) * X
+            const double cmwd = wavex_component<false>(P + Pd.o_cmwx, ncmwx, dd_sub(tdb, pdd(P, Pd.o_cmwx - 2)), 0.0,
+                                                       PINT_COL_CMWX, chain * X, Mb, wr, (unsigned)r, I.n, Pd.runs,
+                                                       Pd.nrun, cmp) * X;
+            tot += cmwd;
+            dsum += cmwd;
+        }
+    }
+    delay[I.roff + r] = tot;
     // The spindown phase at the new total delay: phase(dt - d) = phase(dt) - d F(dt) + d^2 F'(dt) / 2
     // - ..., d = wx + dmd, dt the evaluation's.  The first-order term is kept, as an exact product
     // added in dd; the first dropped term, d^2 |F'(dt)| / 2, is 5e-16 cycle at d = 1 ms and
     // |F1| = 1e-9 Hz/s (F0 <= 1 kHz enters the kept term only: d F <= 1 cycle, whose rounding in dd
     // is below 1e-30) -- six orders below the 1e-10 s x F0 phase bar; d itself is tens of
     // microseconds.
-    const dd ph = dd_sub(dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]), two_prod(wx + dmd, fdt));
+    dd ph = dd_sub(dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]), two_prod(dsum, fdt));
+    if (CHROM && ncm + ncmwx > 0) {
+        // With chromatic terms d = wavex + dmwavex + cm + cmwavex is no longer tens of microseconds
+        // (a scattering delay at 400 MHz reaches milliseconds), so the second-order term
+        // + d^2 F'(dt) / 2 is kept (in double: at d = 1 s and |F1| = 1e-9 Hz/s it is 5e-10 cycle,
+        // its rounding 1e-25).  What is left: the third-order term d^3 |F''| / 6 (2e-21 cycle at
+        // d = 1 s, |F2| = 1e-20 Hz/s^2), and the rounding of F(dt) in the kept first-order product,
+        // 2^-53 d F = 1.1e-13 cycle at d = 1 s and F0 = 1 kHz: below 1e-12 cycle for |d| <= 1 s
+        // (PINT_MAX_ADDED_DELAY).  A row beyond that sets the PINT_E_PARAM status bit and the call
+        // that checks the status fails; pulsars without chromatic terms take the first-order
+        // form above, bit for bit the plain build's.
+        double f1 = 0.0;
+        if (S.nf > 1) {
+            f1 = pval(P, S.o_F + 2 * (S.nf - 1));
+            for (int j = S.nf - 2; j >= 1; j--) f1 = f1 * dtd * inv_int(j) + pval(P, S.o_F + 2 * j);
+        }
+        ph = dd_add_d(ph, 0.5 * dsum * dsum * f1);
+        if (!(fabs(dsum) <= PINT_MAX_ADDED_DELAY)) {
+            atomicOr(status, 1 << PINT_E_PARAM);
+            atomicOr(istatus + blockIdx.x, 1 << PINT_E_PARAM);
+        }
+    }
     ph_hi[I.roff + r] = ph.hi;
     ph_lo[I.roff + r] = ph.lo;
 }
@@ -5795,6 +5880,7 @@ struct pint_ctx {
     int efz = 0;                  // the batch's evaluation blocks carry k_resid1 (EF_ROWS rows + row 0 + TZR)
     bool any_glitch = false;      // an instance's model has glitches: k_glitch follows the evaluation
     bool any_wavex = false;       // ... has WaveX or DMWaveX: k_wavex follows the evaluation (before k_glitch)
+    bool any_chrom = false;       // ... has ChromaticCM / CMWaveX: k_wavex<true> instead (any_wavex is set too)
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
@@ -6728,6 +6814,7 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
     PsrDev& d = ph.dev;
     memset(&d, 0, sizeof(d));
     d.o_wx = d.o_dmwx = -1;  // (pint_set_wavex)
+    d.o_cm = d.o_cmwx = -1;  // (pint_set_chromatic)
     int rc = 0;
     rc |= stg(t->tdb_hi, n + 1, d.tdb_hi);
     rc |= stg(t->tdb_lo, n + 1, d.tdb_lo);
@@ -6891,6 +6978,26 @@ int pint_set_wavex(pint_ctx* ctx, int psr, int o_wx, int nwx, int o_dmwx, int nd
     ph.dev.nwx = nwx;
     ph.dev.o_dmwx = ndmwx > 0 ? o_dmwx : -1;
     ph.dev.ndmwx = ndmwx;
+    ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
+    return PINT_OK;
+}
+
+int pint_set_chromatic(pint_ctx* ctx, int psr, int o_cm, int ncm, int o_cmwx, int ncmwx) {
+    if (!ctx || psr < 0 || psr >= (int)ctx->psrs.size()) return PINT_E_INVALID;
+    PsrHost& ph = ctx->psrs[psr];
+    const long ts = (long)ph.spec.tstride;
+    // the CM terms, CMEPOCH and TNCHROMIDX: ncm + 2 dd pairs at o_cm; the CMWaveX block as in
+    // pint_set_wavex, and only beside a ChromaticCM (whose TNCHROMIDX it takes)
+    const bool bad_cm = ncm < 0 || ncm > PINT_MAX_CM || (ncm > 0 && (o_cm < 0 || (long)o_cm + 2L * (ncm + 2) > ts));
+    const bool bad_wx = ncmwx < 0 || ncmwx > PINT_MAX_WAVEX || (ncmwx > 0 && (ncm < 1 || o_cmwx < 2 || (long)o_cmwx + 6L * ncmwx > ts));
+    if (bad_cm || bad_wx) {
+        ctx->err = "bad ChromaticCM / CMWaveX block or count (PINT_MAX_CM, PINT_MAX_WAVEX; CMWaveX needs ChromaticCM)";
+        return PINT_E_INVALID;
+    }
+    ph.dev.o_cm = ncm > 0 ? o_cm : -1;
+    ph.dev.ncm = ncm;
+    ph.dev.o_cmwx = ncmwx > 0 ? o_cmwx : -1;
+    ph.dev.ncmwx = ncmwx;
     ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
     return PINT_OK;
 }
@@ -7119,6 +7226,13 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
         const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
         ctx->any_wavex = ctx->any_wavex || d.nwx + d.ndmwx > 0;
     }
+    // (nor with chromatic terms: the same pass, in its chromatic build)
+    ctx->any_chrom = false;
+    for (int k = 0; k < ninst; k++) {
+        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
+        ctx->any_chrom = ctx->any_chrom || d.ncm + d.ncmwx > 0;
+    }
+    ctx->any_wavex = ctx->any_wavex || ctx->any_chrom;
     ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch && !ctx->any_wavex;
     long ebn = 0;
     // N-split for the Gram so the launch fills the 256 CUs
@@ -7663,6 +7777,10 @@ static int decode_status(pint_ctx* ctx, int st) {
     if (st & (1 << PINT_E_KEPLER)) { ctx->err = "Kepler equation: eccentricity outside [0,1) or no convergence"; return PINT_E_KEPLER; }
     if (st & (1 << PINT_E_SIGMA)) { ctx->err = "Woodbury Sigma (noise basis) not positive definite"; return PINT_E_SIGMA; }
     if (st & (1 << PINT_E_NOT_PD)) { ctx->err = "normal matrix not positive definite"; return PINT_E_NOT_PD; }
+    if (st == (1 << PINT_E_PARAM)) {
+        ctx->err = "a model's WaveX / DMWaveX / chromatic delays sum to more than 1 s on some row (PINT_MAX_ADDED_DELAY)";
+        return PINT_E_PARAM;
+    }
     if (st) { ctx->err = "device status " + std::to_string(st); return PINT_E_PARAM; }
     return PINT_OK;
 }
@@ -7869,9 +7987,11 @@ int pint_eval(pint_ctx* ctx, int want_M) {
         HIPCHK(hipGetLastError());
     }
     if (ctx->any_wavex) {  // WaveX / DMWaveX: the total delay, the phase at it and their columns (before k_glitch)
-        hipLaunchKernelGGL(k_wavex, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
+        // (a batch with chromatic terms takes the chromatic build; every other batch the plain one)
+        auto kw = ctx->any_chrom ? k_wavex<true> : k_wavex<false>;
+        hipLaunchKernelGGL(kw, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
-                           want_M == 2 ? 1 : 0);
+                           want_M == 2 ? 1 : 0, ctx->d_status, ctx->d_istatus);
         HIPCHK(hipGetLastError());
     }
     if (ctx->any_glitch) {  // Glitch: the phase of every row and the glitch columns, on the evaluation's outputs
@@ -7945,6 +8065,10 @@ int pint_set_wideband(pint_ctx* ctx, int psr, const double* pp_dm, const double*
     if (ph.spec.ndmjump > 0 && !dmjump_mask) { ctx->err = "DMJUMPs without masks"; return PINT_E_INVALID; }
     if (ph.dev.nwx + ph.dev.ndmwx > 0) {  // (DMWaveX's share of the modelled DM and of the DM rows is not formed)
         ctx->err = "wideband DM data with WaveX / DMWaveX is not supported";
+        return PINT_E_INVALID;
+    }
+    if (ph.dev.ncm + ph.dev.ncmwx > 0) {  // (no wideband chromatic fixture exists)
+        ctx->err = "wideband DM data with ChromaticCM / CMWaveX is not supported";
         return PINT_E_INVALID;
     }
     for (int i = 0; i < ph.n; i++)

@@ -54,6 +54,8 @@ class PulsarLayout:
     ep_param: Optional[list] = None  # the ECORR parameter of each epoch
     # WaveX / DMWaveX (pint_set_wavex): (o_wx, nwx, o_dmwx, ndmwx), None for a model with neither
     wavex: Optional[tuple] = None
+    # ChromaticCM / CMWaveX (pint_set_chromatic): (o_cm, ncm, o_cmwx, ncmwx), None for a model with neither
+    chromatic: Optional[tuple] = None
 
 
 def _track_mode(model, toas, track_mode):
@@ -185,6 +187,32 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
             for w, part in enumerate(("SIN", "COS")):
                 place(f"{pre}{part}_{idx:04d}")
                 wx_cols[f"{pre}{part}_{idx:04d}"] = (kind, 2 * k + w)
+    # ChromaticCM: the Taylor terms CM, CM1, ..., then CMEPOCH (0 when unset: every higher term is
+    # then zero, validate) and TNCHROMIDX; CMWaveX: its epoch and block in the form of the WaveX
+    # blocks.  Beside the spec too (pint_set_chromatic)
+    chrom_desc = None
+    cms = model.cm_terms() if "ChromaticCM" in model.components else []
+    if cms:
+        if len(cms) > L.MAX_CM:
+            raise NotImplementedError(f"more than {L.MAX_CM} ChromaticCM Taylor terms (PINT_MAX_CM)")
+        o_cm = pos
+        for j, n in enumerate(cms):
+            place(n)
+            wx_cols[n] = (L.COL_CM, j)
+        place("CMEPOCH")
+        place("TNCHROMIDX")
+        idxs = model.wavex_indices("CMWaveX")
+        if len(idxs) > L.MAX_WAVEX:
+            raise NotImplementedError(f"more than {L.MAX_WAVEX} CMWaveX harmonics (PINT_MAX_WAVEX)")
+        chrom_desc = (o_cm, len(cms), -1, 0)
+        if idxs:
+            place("CMWXEPOCH")
+            chrom_desc = (o_cm, len(cms), pos, len(idxs))
+            for k, idx in enumerate(idxs):
+                place(f"CMWXFREQ_{idx:04d}")
+                for w, part in enumerate(("SIN", "COS")):
+                    place(f"CMWX{part}_{idx:04d}")
+                    wx_cols[f"CMWX{part}_{idx:04d}"] = (L.COL_CMWX, 2 * k + w)
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
                    "DDK": L.BIN_DDK}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
@@ -292,8 +320,9 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
     spec.dmn0 = dmn0 if (use_gls_basis and "PLDMNoise" in model.components) else nred
     lay = PulsarLayout(model=model, toas=toas, n=toas.ntoas, offsets=offs, tstride=tstride, columns=cols,
                        spec=spec, nred=nred, K=len(cols) + 2 * nred, red_freq=rf, red_phi=rp, track_mode=tm)
-    if wx_cols:
+    if any(n > 0 for n in wx_desc[1::2]):
         lay.wavex = tuple(wx_desc)
+    lay.chromatic = chrom_desc
     if ep_lists:
         lay.nep = len(ep_lists)
         lay.ep_ptr = np.concatenate([[0], np.cumsum([len(e) for e in ep_lists])]).astype(np.int32)
@@ -642,6 +671,8 @@ class Session:
                                               L.ptr(lay.ep_idx, C.c_int32), L.ptr(lay.ep_phi)))
         if lay.wavex is not None:
             self._check(self.L.pint_set_wavex(self.ctx, pid, *lay.wavex))
+        if lay.chromatic is not None:
+            self._check(self.L.pint_set_chromatic(self.ctx, pid, *lay.chromatic))
         self.layouts.append(lay)
         return lay
 

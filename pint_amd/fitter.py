@@ -560,7 +560,8 @@ class Fitter:
     def __init__(self, toas, model, track_mode=None, residuals=None):
         # DMWaveX adds to the modelled DM and to the DM design matrix (dmwavex.py:355-387), which
         # the wideband DM rows (k_dm_resid, k_wb_gram) do not form: refuse, do not fit a wrong DM
-        for comp in ("WaveX", "DMWaveX"):
+        # (nor is there a wideband form of the chromatic components' share of the DM rows)
+        for comp in ("WaveX", "DMWaveX", "ChromaticCM", "CMWaveX"):
             if comp in getattr(model, "components", {}) and hasattr(toas, "is_wideband") and toas.is_wideband():
                 raise NotImplementedError(f"wideband TOAs with a {comp} component are outside the supported "
                                           "hot path")

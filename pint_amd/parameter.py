@@ -173,6 +173,11 @@ _DEFS = {
     # WaveX / DMWaveX epochs (wavex.py:51-58, dmwavex.py)
     "WXEPOCH": ("WaveX", "mjd", "d", True, None),
     "DMWXEPOCH": ("DMWaveX", "mjd", "d", True, None),
+    # ChromaticCM (chromatic_model.py:128-169) and the CMWaveX epoch (cmwavex.py:34-41)
+    "CM": ("ChromaticCM", "float", "pc / (cm3 MHz2)", True, None),
+    "CMEPOCH": ("ChromaticCM", "mjd", "d", True, None),
+    "TNCHROMIDX": ("ChromaticCM", "float", "", True, None),
+    "CMWXEPOCH": ("CMWaveX", "mjd", "d", True, None),
     # binaries (pulsar_binary.py, binary_ell1.py, binary_dd.py)
     "PB": ("Binary", "float", "d", True, None),
     "PBDOT": ("Binary", "float", "", False, (1e-12, 1e-7)),
@@ -236,6 +241,11 @@ _PREFIX = {  # prefix params: regex -> (component, units template, long_double)
     r"^DMWXFREQ_(\d{4})$": ("DMWaveX", "1 / d", False),
     r"^DMWXSIN_(\d{4})$": ("DMWaveX", "pc / cm3", False),
     r"^DMWXCOS_(\d{4})$": ("DMWaveX", "pc / cm3", False),
+    # ChromaticCM's Taylor terms (longdouble, per yr^n) and CMWaveX (cmwavex.py:91-136)
+    r"^CM(\d+)$": ("ChromaticCM", "pc / (cm3 MHz2 yr^{n})", True),
+    r"^CMWXFREQ_(\d{4})$": ("CMWaveX", "1 / d", False),
+    r"^CMWXSIN_(\d{4})$": ("CMWaveX", "pc / (cm3 MHz2)", False),
+    r"^CMWXCOS_(\d{4})$": ("CMWaveX", "pc / (cm3 MHz2)", False),
 }
 
 MASK_PARAMS = {"JUMP": ("PhaseJump", "s"), "EFAC": ("ScaleToaError", ""),
@@ -261,7 +271,7 @@ def make_param(name: str) -> Optional[Param]:
             u = units.replace("{n}", str(idx))
             if name == "F0":
                 u = "Hz"
-            if name.startswith("DM") and not name.startswith(("DMX", "DMWX")) and idx == 0:
+            if name.startswith(("DM", "CM")) and not name.startswith(("DMX", "DMWX", "CMWX")) and idx == 0:
                 return None
             return Param(name=name, kind=kind, units=u, long_double=ld, component=comp, index=idx)
     return None

@@ -32,7 +32,8 @@ A model with glitches writes, per glitch in ascending index, GLEP_ GLPH_ GLF0_ G
 GLF0D_ GLTD_, the ones ``setup`` filled in with 0 included (``glitch.py:185-191``).
 A model with WaveX or DMWaveX writes the component's epoch, then ``FREQ_ SIN_ COS_`` of each
 harmonic in parameter order (harmonic 0001, which the component always has, first), after the
-binary's lines; a frequency line carries no fit flag.
+binary's lines; a frequency line carries no fit flag.  ChromaticCM writes CM, CM1, ..., then
+CMEPOCH and TNCHROMIDX (``chromatic_model.py:237-248``); CMWaveX follows it, written like DMWaveX.
 """
 from __future__ import annotations
 
@@ -247,7 +248,7 @@ _ORDER = {
     "PLDMNoise": ["TNDMAMP", "TNDMGAM", "TNDMC"],
 }
 MIDDLE = ["TroposphereDelay", "SolarSystemShapiro", "SolarWindDispersion", "DispersionDM", "DispersionDMX",
-          "Binary", "FD", "WaveX", "DMWaveX", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise",
+          "Binary", "FD", "WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise",
           "ScaleToaError", "PLRedNoise", "PLDMNoise"]
 
 
@@ -264,6 +265,9 @@ def _component_params(model, comp: str) -> List[str]:
     if comp == "DispersionDM":
         return [n for n in ["DM"] if n in names] + _by_index(names, "DM") + \
             [n for n in names if n != "DM" and not (n.startswith("DM") and n[2:].isdigit())]
+    if comp == "ChromaticCM":  # ChromaticCM.print_par (chromatic_model.py:237-248): CM, CMn, then the rest
+        return [n for n in ["CM"] if n in names] + _by_index(names, "CM") + \
+            [n for n in names if n != "CM" and not (n.startswith("CM") and n[2:].isdigit())]
     if comp == "DispersionDMX":  # DMX, then DMX_i, DMXR1_i, DMXR2_i per bin (dispersion_model.py)
         head = [n for n in names if n == "DMX"]
         idx = sorted({int(n.split("_")[1]) for n in names if "_" in n})

@@ -22,7 +22,7 @@ from .parameter import LD, Param
 # components supported on the hot path
 DELAY_ORDER = ["AstrometryEquatorial", "AstrometryEcliptic", "TroposphereDelay", "SolarSystemShapiro",
                "SolarWindDispersion", "DispersionDM", "DispersionDMX", "BinaryELL1", "BinaryDD", "FD", "WaveX",
-               "DMWaveX"]
+               "DMWaveX", "ChromaticCM", "CMWaveX"]
 PHASE_ORDER = ["AbsPhase", "Spindown", "Glitch", "PhaseOffset", "PhaseJump"]
 NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
 
@@ -35,7 +35,11 @@ GLITCH_DECLARED = ("GLPH_", "GLEP_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_
 # WaveX / DMWaveX (wavex.py, dmwavex.py): component -> parameter-name stem.  wavex is the last
 # category of the reference's DEFAULT_ORDER and dmwavex is not in it (it sorts after everything,
 # timing_model.py:1296): both delays follow the binary's, and their parameters follow its.
-WAVEX_STEMS = {"WaveX": "WX", "DMWaveX": "DMWX"}
+# ChromaticCM (category chromatic_constant) and CMWaveX (cmwavex) are not in DEFAULT_ORDER either: in
+# the reference DMWaveX, ChromaticCM and CMWaveX follow everything else in the order its model
+# builder adds them (a set's iteration order: it changes with the hash seed).  Here the order is
+# always ... binary, WaveX, DMWaveX, ChromaticCM, CMWaveX, for the delays and for the parameters.
+WAVEX_STEMS = {"WaveX": "WX", "DMWaveX": "DMWX", "CMWaveX": "CMWX"}
 
 ELL1_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "EDOT", "OMDOT", "M2", "SINI", "TASC", "EPS1", "EPS2",
                "EPS1DOT", "EPS2DOT"]
@@ -235,6 +239,48 @@ class TimingModel:
     def fd_terms(self) -> List[str]:
         return self.prefix_list(r"^FD(\d+)$")
 
+    def cm_terms(self) -> List[str]:
+        """ChromaticCM's Taylor terms CM, CM1, ... in ascending order ([] without the component)."""
+        return ["CM"] + self.prefix_list(r"^CM(\d+)$") if "CM" in self._params else []
+
+    def get_CM_terms(self):
+        """ChromaticCM.get_CM_terms (chromatic_model.py:207-209): the values [CM, CM1, ..., CMn]."""
+        return [self._params[n].value for n in self.cm_terms()]
+
+    def change_cmepoch(self, new_epoch):
+        """ChromaticCM.change_cmepoch (chromatic_model.py:272-302): move CMEPOCH to `new_epoch`
+        (MJD, TDB) and the Taylor terms with it, CM_n <- sum_{k>=n} CM_k dt^(k-n) / (k-n)!, dt in
+        years (taylor_horner_deriv, in longdouble)."""
+        new_epoch = LD(new_epoch)
+        names = self.cm_terms()
+        terms = [LD(0) if self._params[n].value is None else LD(self._params[n].value) for n in names]
+        if self.CMEPOCH.value is None:
+            if any(t != 0 for t in terms[1:]):
+                raise ValueError(f"CMEPOCH not set but some CM derivatives are not zero: {terms}")
+            self.CMEPOCH.value = new_epoch
+        dt = (new_epoch - LD(self.CMEPOCH.value)) / LD(365.25)
+        for n, name in enumerate(names):
+            # taylor_horner_deriv(dt, [0, CM, CM1, ...], n + 1): Horner from the highest term down
+            der = terms[n:]
+            r, fact = LD(0), LD(len(der))
+            for c in der[::-1]:
+                r = r * dt / fact + c
+                fact -= 1
+            self._params[name].value = r
+        self.CMEPOCH.value = new_epoch
+
+    def add_cmwavex_component(self, cmwxfreq, index=None, cmwxsin=0, cmwxcos=0, frozen=True):
+        """CMWaveX.add_cmwavex_component (cmwavex.py:47-138)."""
+        return self.add_wavex_component(cmwxfreq, index, cmwxsin, cmwxcos, frozen, component="CMWaveX")
+
+    def add_cmwavex_components(self, cmwxfreqs, indices=None, cmwxsins=0, cmwxcoses=0, frozens=True):
+        """CMWaveX.add_cmwavex_components (cmwavex.py:140-252)."""
+        return self.add_wavex_components(cmwxfreqs, indices, cmwxsins, cmwxcoses, frozens, component="CMWaveX")
+
+    def remove_cmwavex_component(self, index):
+        """CMWaveX.remove_cmwavex_component (cmwavex.py:254-276)."""
+        self.remove_wavex_component(index, component="CMWaveX")
+
     def glitch_indices(self) -> List[int]:
         """The glitch indices that appear in any GL*_n parameter, ascending (glitch.py:139-145)."""
         return self._names_of("glitch", lambda: sorted({p.index for p in self._params.values()
@@ -398,6 +444,15 @@ class TimingModel:
                                        f"GLTD_{idx} parameter")
         for comp in WAVEX_STEMS:
             self.validate_wavex(comp)
+        if "ChromaticCM" in self.components:  # ChromaticCM.validate (chromatic_model.py:183-199)
+            cm1 = self._params.get("CM1")
+            if cm1 is not None and cm1.value is not None and cm1.value != 0.0 and self.CMEPOCH.value is None:
+                if self.PEPOCH.value is None:
+                    raise MissingParameter("CMEPOCH or PEPOCH is required if CM1 or higher are set")
+                self.CMEPOCH.value = LD(self.PEPOCH.value)
+        if "CMWaveX" in self.components and "ChromaticCM" not in self.components:
+            # (the reference fails only when the delay is first evaluated, with a KeyError on TNCHROMIDX)
+            raise TimingModelError("CMWaveX needs a ChromaticCM component (its TNCHROMIDX is the chromatic index)")
         if self.binary in ("DD", "BT", "DDK"):
             e = float(self.ECC.value or 0.0)
             if not (0 <= e < 1):
@@ -542,7 +597,7 @@ def get_model(parfile) -> TimingModel:
         defaults += [("SWM", 0)]
     if any(n == "DM" or re.match(r"^DM\d+$", n) for n in names):
         defaults += [("DM", LD(0)), ("DMEPOCH", None)]
-    wavex_rx = re.compile(r"^(DM)?WX(EPOCH|(FREQ|SIN|COS)_\d+)$")
+    wavex_rx = re.compile(r"^(DM|CM)?WX(EPOCH|(FREQ|SIN|COS)_\d+)$")
     if binary in ("ELL1", "ELL1H"):
         defaults += [(n, 0.0) for n in ELL1_PARAMS if not (binary == "ELL1H" and n in ("M2", "SINI"))]
         defaults += [("TASC", None)]
@@ -571,8 +626,14 @@ def get_model(parfile) -> TimingModel:
         if p.component == "Binary":
             p.component = "Binary"
         model.add_param(p)
-    # WaveX, then DMWaveX, after the binary's parameters (the components as constructed)
+    # WaveX, DMWaveX, ChromaticCM, then CMWaveX, after the binary's parameters (the components as
+    # constructed; ChromaticCM, chromatic_model.py:128-169: CM 0, CM1 unset, CMEPOCH unset, TNCHROMIDX 4)
     for comp, stem in WAVEX_STEMS.items():
+        if comp == "CMWaveX" and any(n in ("CM", "CMEPOCH", "TNCHROMIDX") or re.match(r"^CM\d+$", n) for n in names):
+            for n, v in (("CM", LD(0)), ("CM1", None), ("CMEPOCH", None), ("TNCHROMIDX", LD(4))):
+                p = P.make_param(n)
+                p.value = v
+                model.add_param(p)
         if any(re.match(rf"^{stem}(EPOCH|(FREQ|SIN|COS)_\d{{4}})$", n) for n in names):
             model._ensure_wavex(comp)
     for l in lines:

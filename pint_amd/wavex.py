@@ -5,7 +5,8 @@ get_wavex_amps).
 The components themselves live in ``TimingModel`` (``add_wavex_component(s)``,
 ``remove_wavex_component``, ``get_wavex_indices``); their delays and design-matrix columns are
 the device kernel ``k_wavex``.  Frequencies are in 1 / d, WaveX amplitudes in s, DMWaveX
-amplitudes in pc / cm3.  Not provided: ``find_optimal_nharms``, ``plrednoise_from_wavex``,
+amplitudes in pc / cm3, CMWaveX amplitudes in pc / cm3 / MHz2 (``cmwavex_setup``,
+``utils.py:1645-1736``; ``get_wavex_freqs`` / ``get_wavex_amps`` are WaveX's alone, as in the reference).  Not provided: ``find_optimal_nharms``, ``plrednoise_from_wavex``,
 ``pldmnoise_from_dmwavex`` and the Wave <-> WaveX translations.
 """
 from __future__ import annotations
@@ -16,7 +17,7 @@ import numpy as np
 
 from .timing_model import WAVEX_STEMS
 
-__all__ = ["wavex_setup", "dmwavex_setup", "get_wavex_freqs", "get_wavex_amps"]
+__all__ = ["wavex_setup", "dmwavex_setup", "cmwavex_setup", "get_wavex_freqs", "get_wavex_amps"]
 
 
 def _setup(model, comp, T_span, freqs, n_freqs, freeze_params):
@@ -34,7 +35,7 @@ def _setup(model, comp, T_span, freqs, n_freqs, freeze_params):
     if freqs is not None:
         freqs = np.sort(np.atleast_1d(np.asarray(freqs, dtype=np.float64)))
         if len(freqs) > 1 and np.min(np.diff(freqs)) < 1.0 / (2.0 * T_span):
-            warnings.warn(("Wave" if comp == "WaveX" else "DMWaveX") +
+            warnings.warn(("Wave" if comp == "WaveX" else comp) +
                           " frequency spacing is finer than frequency resolution of data")
     else:
         freqs = np.arange(1, n_freqs + 1) / T_span
@@ -57,6 +58,12 @@ def wavex_setup(model, T_span, freqs=None, n_freqs=None, freeze_params=False):
 def dmwavex_setup(model, T_span, freqs=None, n_freqs=None, freeze_params=False):
     """wavex_setup for DMWaveX."""
     return _setup(model, "DMWaveX", T_span, freqs, n_freqs, freeze_params)
+
+
+def cmwavex_setup(model, T_span, freqs=None, n_freqs=None, freeze_params=False):
+    """wavex_setup for CMWaveX (``utils.py:1645-1736``); amplitudes in pc / cm3 / MHz2.  The model
+    needs a ChromaticCM component (CM, TNCHROMIDX) before it validates or evaluates."""
+    return _setup(model, "CMWaveX", T_span, freqs, n_freqs, freeze_params)
 
 
 def _select(model, index, pick):

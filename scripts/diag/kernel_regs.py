@@ -4,7 +4,9 @@
   python scripts/diag/kernel_regs.py new.txt [old.txt] [name filter, default k_eval|k_glitch|k_wavex]
 
 With two files: every kernel of either whose name matches, side by side, and whether the figures
-are equal (the register gate of a change that must leave the evaluation's builds alone).
+are equal (the register gate of a change that must leave the evaluation's builds alone).  k_wavex
+is a template since the chromatic components: its plain build, k_wavex<false>, is compared with a
+parent's untemplated k_wavex; the chromatic build, k_wavex<true>, is listed as new.
 """
 import re
 import subprocess
@@ -40,6 +42,12 @@ if __name__ == "__main__":
     old = read(files[1]) if len(files) > 1 else None
     names = [n for n in dict.fromkeys(list(new) + list(old or {})) if rx.search(n)]
     pretty = demangle(names)
+    if old is not None:  # (the plain build of a kernel that became a template stands for the parent's)
+        plain = {re.sub(r"^void |<false>$", "", pretty[n]): n for n in names if n in new and pretty[n].endswith("<false>")}
+        for n in list(names):
+            if n in old and n not in new and pretty[n] in plain:
+                old[plain[pretty[n]]] = old[n]
+                names.remove(n)
     fmt = lambda d: "-" if d is None else f"{d['VGPRs']:4d} VGPRs {d['ScratchSize']:4d} B {d['Occupancy']:2d} waves"
     same = True
     for n in names:
