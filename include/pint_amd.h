@@ -47,7 +47,11 @@ extern "C" {
 #define PINT_MAX_CM 16        /* ChromaticCM Taylor terms CM, CM1, ... per model                        */
 #define PINT_MAX_ADDED_DELAY 1.0 /* s: the largest |WaveX + DMWaveX + ChromaticCM + CMWaveX| delay of a row
                                  for which the phase moved to it holds 1e-12 cycle (k_wavex); a model
-                                 beyond it fails with PINT_E_PARAM                                     */
+                                 beyond it fails with PINT_E_PARAM.  The same bound, on its own, for
+                                 |FDJump + FDJumpDM| (k_fdjump)                                        */
+#define PINT_MAX_FDJUMP 64    /* FDJump parameters, and FDJumpDM parameters, per model: one 64-bit mask
+                                 word per row and family                                               */
+#define PINT_FDJUMP_MAX_INDEX 20 /* the largest FD index p of FD{p}JUMP{q} (fdjump.py:12)                */
 
 /* ---- per-TOA packed input (reference TOAs.table columns
  *      toa.py:2320 tdbld, :2385-2439 posvels, freq, error, mjd_float, pulse_number) ---- */
@@ -123,9 +127,15 @@ enum {
     PINT_COL_CM = 17,       /* CM, CM1, ...: col_index = the Taylor order k; d_delay_d_p = DMconst
                                bfreq^(-TNCHROMIDX) dt^k / k!, dt years since CMEPOCH
                                (chromatic_model.py:64-90, :250-270)                                   */
-    PINT_COL_CMWX = 18      /* CMWXSIN_ / CMWXCOS_: col_index = 2 k + (0 sin, 1 cos); d_cm_d_p = sin / cos
+    PINT_COL_CMWX = 18,     /* CMWXSIN_ / CMWXCOS_: col_index = 2 k + (0 sin, 1 cos); d_cm_d_p = sin / cos
                                (2 pi CMWXFREQ_k (tdb - CMWXEPOCH)), times DMconst bfreq^(-TNCHROMIDX)
                                (cmwavex.py:373-387)                                                   */
+    PINT_COL_FDJUMP = 19,   /* FD{p}JUMP{q}: col_index = the parameter's place in pint_set_fdjump's block
+                               (ascending p), also its bit in the row masks; d_delay_d_p = y^p on the
+                               rows its mask selects, 0 elsewhere (fdjump.py:177-193)                  */
+    PINT_COL_FDJUMPDM = 20  /* FDJUMPDM{q}: col_index = the place in the FDJumpDM block and the mask bit;
+                               d_delay_d_p = -DMconst / bfreq^2 on the selected rows
+                               (dispersion_model.py:877-884, :99-109)                                  */
 };
 /* the parameters of one glitch, in the order of its 7 table slots (glitch.py:130-138 glitch_prop) */
 enum {
@@ -264,6 +274,24 @@ int pint_set_wavex(pint_ctx *ctx, int psr, int o_wx, int nwx, int o_dmwx, int nd
  * before.  The four delays of a row may sum to at most PINT_MAX_ADDED_DELAY.  Same calling
  * rule as pint_set_wavex; a model with neither component makes no call. */
 int pint_set_chromatic(pint_ctx *ctx, int psr, int o_cm, int ncm, int o_cmwx, int ncmwx);
+/* FDJump / FDJumpDM (fdjump.py, dispersion_model.py:805-884) of pulsar `psr`, described beside
+ * the spec like WaveX: system-dependent delays selected per row by a mask.
+ *   FDJump    nfdj (<= PINT_MAX_FDJUMP) values (s) as dd pairs at table slot o_fdj, value k of FD
+ *             index fd_index[k] in 1..PINT_FDJUMP_MAX_INDEX, non-decreasing in k; bit k of
+ *             mask[r] says that row r is selected by parameter k.  delay = sum_k [bit k] value_k
+ *             y^fd_index[k], y = log(bfreq / 1 GHz) when use_log, else bfreq / 1 GHz; a
+ *             non-finite y is 0 (fdjump.py:122-175);
+ *   FDJumpDM  nfdjdm (<= PINT_MAX_FDJUMP) values (pc cm^-3) at o_fdjdm, bit k of dmmask[r]:
+ *             delay = DMconst / bfreq^2 * sum_k [bit k] (-value_k).
+ * mask and dmmask have n + 1 entries, the last the TZR TOA's; the library keeps device copies of
+ * its own and frees them with the pulsar's other arrays; a family with no parameter may pass a
+ * null mask.  Both delays follow WaveX, DMWaveX, ChromaticCM and CMWaveX in the delay sum, in this
+ * order, in a pass of their own (k_fdjump, after k_wavex and before k_glitch); a batch without
+ * them launches what it launched before.  The two delays of a row may sum to at most
+ * PINT_MAX_ADDED_DELAY.  Wideband DM data with either is refused (pint_set_wideband).  Same
+ * calling rule as pint_set_wavex; a model with neither component makes no call. */
+int pint_set_fdjump(pint_ctx *ctx, int psr, int o_fdj, int nfdj, const int32_t *fd_index, int use_log,
+                    const uint64_t *mask, int o_fdjdm, int nfdjdm, const uint64_t *dmmask);
 
 /* Bind `ninst` instances (grid points, PTA pulsars, trial states): inst_psr[k] is a
  * pulsar id; `tables` concatenates each instance's parameter table (spec.tstride doubles,

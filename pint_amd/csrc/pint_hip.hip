@@ -116,6 +116,12 @@ struct PsrDev {
     // ChromaticCM / CMWaveX (pint_set_chromatic): the CM Taylor terms' slot and count (CMEPOCH's pair
     // at o_cm + 2 ncm, TNCHROMIDX's after it), the CMWaveX block like a WaveX block
     int o_cm, ncm, o_cmwx, ncmwx;
+    // FDJump / FDJumpDM (pint_set_fdjump): each family's block of values (dd pairs) and count, the
+    // FD index of each FDJump value (ascending), log or linear frequency, and the per-row mask
+    // words (n + 1; bit k: the row is selected by the family's parameter k)
+    int o_fdj, nfdj, o_fdjdm, nfdjdm, fdj_log;
+    const int32_t* fdj_index;
+    const uint64_t *fdjmask, *fdjdmmask;
 };
 
 struct InstDev {
@@ -857,6 +863,124 @@ __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, 
             atomicOr(status, 1 << PINT_E_PARAM);
             atomicOr(istatus + blockIdx.x, 1 << PINT_E_PARAM);
         }
+    }
+    ph_hi[I.roff + r] = ph.hi;
+    ph_lo[I.roff + r] = ph.lo;
+}
+
+// k_fdjump: the FDJump and FDJumpDM components (fdjump.py:122-193, dispersion_model.py:859-884) of
+// the instances whose model has either (pint_set_fdjump), after k_wavex and before k_glitch (whose
+// dt takes the total delay), on the evaluation's outputs.  Neither delay reads the accumulated
+// delay, so like the other post-evaluation components they are a pass of their own and no
+// k_eval* or k_wavex build changes.  Per evaluation row (TOAs and the TZR row), with bfreq the
+// barycentric radio frequency as k_wavex forms it:
+//   FDJump    y = log(bfreq / 1 GHz) (FDJUMPLOG Y, the constructor's value) or bfreq / 1 GHz, a
+//             non-finite y replaced by 0 (get_freq_y, :122-150); delay = sum_k [row selected by
+//             parameter k's mask] value_k y^p_k; overlapping masks add (:165-173);
+//   FDJumpDM  delay = DMconst / bfreq^2 * sum_k [selected] (-value_k) (fdjump_dm, :859-871).
+// The reference's DelayComponent_list ends ... WaveX, DMWaveX, ChromaticCM, CMWaveX, FDJump,
+// FDJumpDM in the run the fixtures were captured in (fdjump and fdjumpdm are not categories of
+// DEFAULT_ORDER either: see k_wavex); the total is ((D + fdjump) + fdjumpdm), D what k_wavex left.
+// One thread per row; grid (instances, row blocks of the longest instance).  The parameter loops
+// are wave-uniform: value and FD index come from the table and the descriptor at uniform
+// addresses, the block is sorted by FD index so one running power of y serves every parameter,
+// and the add is predicated on the row's mask bit (no per-lane loop over set bits).  With Mout
+// every row of every free PINT_COL_FDJUMP / PINT_COL_FDJUMPDM column is written, chain * y^p or
+// chain * (-DMconst / bfreq^2) on the selected rows and 0 on the others (coalesced; nothing relies
+// on the evaluation's zero fill), in the full or the compact fit layout.  A kind's runs are
+// adjacent (its columns are), so each parameter scans only those.
+//
+// Phase: moved to the new total delay as k_wavex<true> does, phase(dt - d) = phase(dt) - d F(dt)
+// + d^2 F'(dt) / 2 with d = fdjump + fdjumpdm (tens of microseconds for real systems), the
+// first-order product exact in dd; the same bound |d| <= PINT_MAX_ADDED_DELAY holds 1e-12 cycle
+// and a row beyond it sets the PINT_E_PARAM status bits.
+__global__ __launch_bounds__(256) void k_fdjump(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
+                                                const double* __restrict__ tables, const InstConst* __restrict__ ic,
+                                                double* __restrict__ delay, double* __restrict__ ph_hi,
+                                                double* __restrict__ ph_lo, double* __restrict__ Mout, int compact,
+                                                int* __restrict__ status, int* __restrict__ istatus) {
+    const InstDev I = insts[blockIdx.x];
+    const PsrDev& Pd = psrs[I.psr];
+    const int nfdj = Pd.nfdj, nfdjdm = Pd.nfdjdm;
+    if (nfdj + nfdjdm <= 0) return;  // (block-uniform)
+    const int r = blockIdx.y * 256 + threadIdx.x;
+    if (r > I.n) return;
+    const pint_spec_t& S = *Pd.spec;
+    const double* P = tables + I.toff;
+    const InstConst& C = ic[blockIdx.x];
+    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
+    const double D = delay[I.roff + r];
+    // the spin frequency at the row's delay so far: the chain factor of the delay columns (k_wavex)
+    const double dtd = dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(P, S.o_PEPOCH)), DAYSEC), -D));
+    const double fdt = spin_freq(S, P, dtd);
+    const double chain = fdt * C.iF0;
+    double* Mb = Mout ? Mout + I.moff : nullptr;
+    const bool wr = Mb && r < I.n, cmp = compact && Pd.dsplit;
+    const long ld = I.n;
+    // the barycentric radio frequency, as eval_pre and k_wavex form it (astrometry.py:359-364)
+    double bfreq = Pd.freq[r];
+    if (S.astrometry) {
+        double L[3];
+        psr_dir_icrs(C, dd_to_d(tdb), L);
+        const double vdl = Pd.vel[3 * r] * L[0] + Pd.vel[3 * r + 1] * L[1] + Pd.vel[3 * r + 2] * L[2];
+        bfreq *= 1.0 - vdl * INV_C_KMS;
+    }
+    const ColRun* runs = Pd.runs;
+    const int nrun = Pd.nrun;
+    double fd = 0.0, dmd = 0.0;
+    for (int fam = 0; fam < 2; fam++) {  // 0: FDJump, 1: FDJumpDM
+        const int np = fam ? nfdjdm : nfdj;
+        if (np <= 0) continue;
+        const int kind = fam ? PINT_COL_FDJUMPDM : PINT_COL_FDJUMP;
+        int u0 = 0, u1 = 0;
+        if (Mb) {
+            u0 = nrun;
+            for (int u = 0; u < nrun; u++)
+                if (runs[u].kind == kind) {
+                    u0 = u < u0 ? u : u0;
+                    u1 = u + 1;
+                }
+        }
+        const unsigned long long m = (fam ? Pd.fdjdmmask : Pd.fdjmask)[r];
+        const double* B = P + (fam ? Pd.o_fdjdm : Pd.o_fdj);
+        double y = 0.0, yp = 0.0;  // yp: y^p at the current FD index p; FDJumpDM: the column value
+        int p = 1;
+        if (fam) {
+            yp = -DMCONST / (bfreq * bfreq);  // d_delay_d_dmparam x d_dm_d_fdjumpdm = -1 (:99-109, :877-884)
+        } else {
+            y = Pd.fdj_log ? log(bfreq * 1e-3) : bfreq * 1e-3;  // (freq.to(GHz), fdjump.py:142-146)
+            if (!isfinite(y)) y = 0.0;
+            yp = y;
+        }
+        double acc = 0.0;
+        for (int k = 0; k < np; k++) {
+            if (!fam)
+                for (const int pk = Pd.fdj_index[k]; p < pk; p++) yp *= y;  // (uniform: the block ascends in p)
+            const bool sel = (m >> k) & 1ULL;
+            // FDJump: value y^p; FDJumpDM: the DM offset -value (the delay's factor comes after the sum)
+            acc += sel ? (fam ? -pval(B, 2 * k) : pval(B, 2 * k) * yp) : 0.0;
+            for (int u = u0; u < u1; u++) {
+                const ColRun R = runs[u];
+                if (R.kind != kind) continue;
+                const int j = k - R.idx0;
+                if (wr && j >= 0 && j < R.cnt) Mb[((long)(cmp ? R.dcol0 : R.col0) + j) * ld + r] = sel ? chain * yp : 0.0;
+            }
+        }
+        if (fam) dmd = acc * DMCONST / (bfreq * bfreq);  // dispersion_time_delay (dispersion_model.py:42-52)
+        else fd = acc;
+    }
+    const double dsum = fd + dmd;
+    delay[I.roff + r] = (D + fd) + dmd;
+    double f1 = 0.0;
+    if (S.nf > 1) {
+        f1 = pval(P, S.o_F + 2 * (S.nf - 1));
+        for (int j = S.nf - 2; j >= 1; j--) f1 = f1 * dtd * inv_int(j) + pval(P, S.o_F + 2 * j);
+    }
+    dd ph = dd_sub(dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]), two_prod(dsum, fdt));
+    ph = dd_add_d(ph, 0.5 * dsum * dsum * f1);
+    if (!(fabs(dsum) <= PINT_MAX_ADDED_DELAY)) {
+        atomicOr(status, 1 << PINT_E_PARAM);
+        atomicOr(istatus + blockIdx.x, 1 << PINT_E_PARAM);
     }
     ph_hi[I.roff + r] = ph.hi;
     ph_lo[I.roff + r] = ph.lo;
@@ -5881,6 +6005,7 @@ struct pint_ctx {
     bool any_glitch = false;      // an instance's model has glitches: k_glitch follows the evaluation
     bool any_wavex = false;       // ... has WaveX or DMWaveX: k_wavex follows the evaluation (before k_glitch)
     bool any_chrom = false;       // ... has ChromaticCM / CMWaveX: k_wavex<true> instead (any_wavex is set too)
+    bool any_fdjump = false;      // ... has FDJump / FDJumpDM: k_fdjump follows k_wavex (before k_glitch)
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
@@ -6815,6 +6940,7 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
     memset(&d, 0, sizeof(d));
     d.o_wx = d.o_dmwx = -1;  // (pint_set_wavex)
     d.o_cm = d.o_cmwx = -1;  // (pint_set_chromatic)
+    d.o_fdj = d.o_fdjdm = -1;  // (pint_set_fdjump)
     int rc = 0;
     rc |= stg(t->tdb_hi, n + 1, d.tdb_hi);
     rc |= stg(t->tdb_lo, n + 1, d.tdb_lo);
@@ -6998,6 +7124,58 @@ int pint_set_chromatic(pint_ctx* ctx, int psr, int o_cm, int ncm, int o_cmwx, in
     ph.dev.ncm = ncm;
     ph.dev.o_cmwx = ncmwx > 0 ? o_cmwx : -1;
     ph.dev.ncmwx = ncmwx;
+    ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
+    return PINT_OK;
+}
+
+int pint_set_fdjump(pint_ctx* ctx, int psr, int o_fdj, int nfdj, const int32_t* fd_index, int use_log,
+                    const uint64_t* mask, int o_fdjdm, int nfdjdm, const uint64_t* dmmask) {
+    if (!ctx) return PINT_E_INVALID;
+    if (psr < 0 || psr >= (int)ctx->psrs.size()) { ctx->err = "pint_set_fdjump: bad pulsar id"; return PINT_E_INVALID; }
+    PsrHost& ph = ctx->psrs[psr];
+    const long ts = (long)ph.spec.tstride;
+    // each family: its count, its block of dd pairs inside the table, its n + 1 mask words with no
+    // bit beyond the count; FDJump's indices in 1..PINT_FDJUMP_MAX_INDEX, ascending
+    auto bad = [&](int o, int n, const uint64_t* m) {
+        if (n < 0 || n > PINT_MAX_FDJUMP) return true;
+        if (n == 0) return false;
+        if (o < 0 || (long)o + 2L * n > ts || !m) return true;
+        if (n < 64)
+            for (int r = 0; r <= ph.n; r++)
+                if (m[r] >> n) return true;
+        return false;
+    };
+    bool bad_idx = nfdj > 0 && !fd_index;
+    for (int k = 0; !bad_idx && k < nfdj && nfdj <= PINT_MAX_FDJUMP; k++)
+        bad_idx = fd_index[k] < 1 || fd_index[k] > PINT_FDJUMP_MAX_INDEX || (k > 0 && fd_index[k] < fd_index[k - 1]);
+    if (bad(o_fdj, nfdj, mask) || bad(o_fdjdm, nfdjdm, dmmask) || bad_idx) {
+        ctx->err = "bad FDJump / FDJumpDM block, count, FD index or row mask (PINT_MAX_FDJUMP, PINT_FDJUMP_MAX_INDEX)";
+        return PINT_E_INVALID;
+    }
+    if (ph.dev.wb) {  // (FDJumpDM adds to the modelled DM, which k_dm_resid / k_wb_gram do not form)
+        ctx->err = "wideband DM data with FDJump / FDJumpDM is not supported";
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    // device copies of the library's own, kept with the pulsar's other allocations (a repeated
+    // call leaves the earlier copies to the pulsar's release)
+    PsrDev& d = ph.dev;
+    d.nfdj = d.nfdjdm = 0;  // (until the copies stand)
+    int rc = 0;
+    if (nfdj > 0) {
+        rc |= upload(ctx, ph, fd_index, (size_t)nfdj, d.fdj_index);
+        rc |= upload(ctx, ph, mask, (size_t)ph.n + 1, d.fdjmask);
+    }
+    if (nfdjdm > 0) rc |= upload(ctx, ph, dmmask, (size_t)ph.n + 1, d.fdjdmmask);
+    if (rc) {
+        ctx->err = "pint_set_fdjump: device allocation or copy failed";
+        return PINT_E_HIP;
+    }
+    d.o_fdj = nfdj > 0 ? o_fdj : -1;
+    d.nfdj = nfdj;
+    d.o_fdjdm = nfdjdm > 0 ? o_fdjdm : -1;
+    d.nfdjdm = nfdjdm;
+    d.fdj_log = use_log ? 1 : 0;
     ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
     return PINT_OK;
 }
@@ -7233,7 +7411,14 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
         ctx->any_chrom = ctx->any_chrom || d.ncm + d.ncmwx > 0;
     }
     ctx->any_wavex = ctx->any_wavex || ctx->any_chrom;
-    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch && !ctx->any_wavex;
+    // (nor with FDJump / FDJumpDM: k_fdjump moves the delay and the phase after the evaluation)
+    ctx->any_fdjump = false;
+    for (int k = 0; k < ninst; k++) {
+        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
+        ctx->any_fdjump = ctx->any_fdjump || d.nfdj + d.nfdjdm > 0;
+    }
+    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch && !ctx->any_wavex &&
+               !ctx->any_fdjump;
     long ebn = 0;
     // N-split for the Gram so the launch fills the 256 CUs
     // choose the split count that minimises (workgroup rounds) / nsplit, i.e. the k_gram
@@ -7778,7 +7963,8 @@ static int decode_status(pint_ctx* ctx, int st) {
     if (st & (1 << PINT_E_SIGMA)) { ctx->err = "Woodbury Sigma (noise basis) not positive definite"; return PINT_E_SIGMA; }
     if (st & (1 << PINT_E_NOT_PD)) { ctx->err = "normal matrix not positive definite"; return PINT_E_NOT_PD; }
     if (st == (1 << PINT_E_PARAM)) {
-        ctx->err = "a model's WaveX / DMWaveX / chromatic delays sum to more than 1 s on some row (PINT_MAX_ADDED_DELAY)";
+        ctx->err = "a model's WaveX / DMWaveX / chromatic delays, or its FDJump / FDJumpDM delays, sum to more than 1 s "
+                   "on some row (PINT_MAX_ADDED_DELAY)";
         return PINT_E_PARAM;
     }
     if (st) { ctx->err = "device status " + std::to_string(st); return PINT_E_PARAM; }
@@ -7994,6 +8180,12 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                            want_M == 2 ? 1 : 0, ctx->d_status, ctx->d_istatus);
         HIPCHK(hipGetLastError());
     }
+    if (ctx->any_fdjump) {  // FDJump / FDJumpDM: their delays, the phase at the new total, their columns
+        hipLaunchKernelGGL(k_fdjump, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
+                           want_M == 2 ? 1 : 0, ctx->d_status, ctx->d_istatus);
+        HIPCHK(hipGetLastError());
+    }
     if (ctx->any_glitch) {  // Glitch: the phase of every row and the glitch columns, on the evaluation's outputs
         hipLaunchKernelGGL(k_glitch, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
@@ -8065,6 +8257,10 @@ int pint_set_wideband(pint_ctx* ctx, int psr, const double* pp_dm, const double*
     if (ph.spec.ndmjump > 0 && !dmjump_mask) { ctx->err = "DMJUMPs without masks"; return PINT_E_INVALID; }
     if (ph.dev.nwx + ph.dev.ndmwx > 0) {  // (DMWaveX's share of the modelled DM and of the DM rows is not formed)
         ctx->err = "wideband DM data with WaveX / DMWaveX is not supported";
+        return PINT_E_INVALID;
+    }
+    if (ph.dev.nfdj + ph.dev.nfdjdm > 0) {  // (FDJumpDM adds to the modelled DM: the DM rows do not form it)
+        ctx->err = "wideband DM data with FDJump / FDJumpDM is not supported";
         return PINT_E_INVALID;
     }
     if (ph.dev.ncm + ph.dev.ncmwx > 0) {  // (no wideband chromatic fixture exists)

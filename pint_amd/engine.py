@@ -56,6 +56,9 @@ class PulsarLayout:
     wavex: Optional[tuple] = None
     # ChromaticCM / CMWaveX (pint_set_chromatic): (o_cm, ncm, o_cmwx, ncmwx), None for a model with neither
     chromatic: Optional[tuple] = None
+    # FDJump / FDJumpDM (pint_set_fdjump): (o_fdj, nfdj, fd_index int32[nfdj], use_log, mask uint64[n + 1],
+    # o_fdjdm, nfdjdm, dmmask uint64[n + 1]), None for a model with neither
+    fdjump: Optional[tuple] = None
 
 
 def _track_mode(model, toas, track_mode):
@@ -213,6 +216,33 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
                 for w, part in enumerate(("SIN", "COS")):
                     place(f"CMWX{part}_{idx:04d}")
                     wx_cols[f"CMWX{part}_{idx:04d}"] = (L.COL_CMWX, 2 * k + w)
+    # FDJump / FDJumpDM: the values of each family in one block of dd pairs, FDJump's ordered by FD
+    # index (stable: the device advances one running power of y through them), FDJumpDM's in
+    # parameter order; col_index = the position in the block, which is also the parameter's bit in
+    # the family's per-row mask word (n + 1 words, the last the TZR TOA's).  Beside the spec
+    # (pint_set_fdjump)
+    fdj_desc = None
+    fdjs = sorted(model.fdjump_params(), key=model.get_fd_index)
+    fdjdms = model.fdjumpdm_params()
+    if fdjs or fdjdms:
+        for group, what in ((fdjs, "FDJump"), (fdjdms, "FDJumpDM")):
+            if len(group) > L.MAX_FDJUMP:
+                raise NotImplementedError(f"more than {L.MAX_FDJUMP} {what} parameters (PINT_MAX_FDJUMP)")
+        starts, masks = [], []
+        for group, kind in ((fdjs, L.COL_FDJUMP), (fdjdms, L.COL_FDJUMPDM)):
+            starts.append(pos if group else -1)
+            m = np.zeros(toas.ntoas + 1, dtype=np.uint64)
+            for k, n in enumerate(group):
+                place(n)
+                wx_cols[n] = (kind, k)
+                p = model[n]
+                m[toas.select_mask(p.key, p.key_value)] |= np.uint64(1) << np.uint64(k)
+                if len(toas.select_mask(p.key, p.key_value, tzr=True)) if toas.tzr else False:
+                    m[toas.ntoas] |= np.uint64(1) << np.uint64(k)
+            masks.append(m)
+        use_log = 1 if ("FDJUMPLOG" not in model or model.FDJUMPLOG.value) else 0
+        fdj_desc = (starts[0], len(fdjs), np.array([model.get_fd_index(n) for n in fdjs] or [0], dtype=np.int32),
+                    use_log, masks[0], starts[1], len(fdjdms), masks[1])
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
                    "DDK": L.BIN_DDK}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
@@ -323,6 +353,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
     if any(n > 0 for n in wx_desc[1::2]):
         lay.wavex = tuple(wx_desc)
     lay.chromatic = chrom_desc
+    lay.fdjump = fdj_desc
     if ep_lists:
         lay.nep = len(ep_lists)
         lay.ep_ptr = np.concatenate([[0], np.cumsum([len(e) for e in ep_lists])]).astype(np.int32)
@@ -673,6 +704,10 @@ class Session:
             self._check(self.L.pint_set_wavex(self.ctx, pid, *lay.wavex))
         if lay.chromatic is not None:
             self._check(self.L.pint_set_chromatic(self.ctx, pid, *lay.chromatic))
+        if lay.fdjump is not None:
+            o_fdj, nfdj, fdidx, use_log, mask, o_dm, ndm, dmmask = lay.fdjump
+            self._check(self.L.pint_set_fdjump(self.ctx, pid, o_fdj, nfdj, L.ptr(fdidx, C.c_int32), use_log,
+                                               L.ptr(mask, C.c_uint64), o_dm, ndm, L.ptr(dmmask, C.c_uint64)))
         self.layouts.append(lay)
         return lay
 

@@ -561,7 +561,8 @@ class Fitter:
         # DMWaveX adds to the modelled DM and to the DM design matrix (dmwavex.py:355-387), which
         # the wideband DM rows (k_dm_resid, k_wb_gram) do not form: refuse, do not fit a wrong DM
         # (nor is there a wideband form of the chromatic components' share of the DM rows)
-        for comp in ("WaveX", "DMWaveX", "ChromaticCM", "CMWaveX"):
+        # (FDJumpDM adds -FDJUMPDM to the modelled DM of its TOAs, dispersion_model.py:859-871, like DMWaveX)
+        for comp in ("WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM"):
             if comp in getattr(model, "components", {}) and hasattr(toas, "is_wideband") and toas.is_wideband():
                 raise NotImplementedError(f"wideband TOAs with a {comp} component are outside the supported "
                                           "hot path")

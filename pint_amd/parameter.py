@@ -178,6 +178,8 @@ _DEFS = {
     "CMEPOCH": ("ChromaticCM", "mjd", "d", True, None),
     "TNCHROMIDX": ("ChromaticCM", "float", "", True, None),
     "CMWXEPOCH": ("CMWaveX", "mjd", "d", True, None),
+    # FDJump's switch (fdjump.py:69-75): log(f / GHz) (Y) or f / GHz (N) as the polynomial's argument
+    "FDJUMPLOG": ("FDJump", "bool", "", False, None),
     # binaries (pulsar_binary.py, binary_ell1.py, binary_dd.py)
     "PB": ("Binary", "float", "d", True, None),
     "PBDOT": ("Binary", "float", "", False, (1e-12, 1e-7)),
@@ -255,6 +257,24 @@ MASK_PARAMS = {"JUMP": ("PhaseJump", "s"), "EFAC": ("ScaleToaError", ""),
                # ScaleDmError): DM offsets and DM-error scaling, pc/cm^3
                "DMJUMP": ("DispersionJump", "pc / cm3"), "DMEFAC": ("ScaleDmError", ""),
                "DMEQUAD": ("ScaleDmError", "pc / cm3")}
+
+# FDJump (fdjump.py:76-84): mask parameters FD{p}JUMP{q}, p = the FD index 1..fdjump_max_index, q
+# the mask index; the base name of a par line is FD{p}JUMP (tempo2's FDJUMP{p} is the same
+# parameter, model_builder._replace_fdjump_in_parfile_dict).  FDJumpDM (dispersion_model.py:805-
+# 884): FDJUMPDM{q}, a DM offset of -value on the selected TOAs
+FDJUMP_MAX_INDEX = 20
+MASK_PARAMS.update({f"FD{_j}JUMP": ("FDJump", "s") for _j in range(1, FDJUMP_MAX_INDEX + 1)})
+MASK_PARAMS["FDJUMPDM"] = ("FDJumpDM", "pc / cm3")
+FDJUMP_NAME = re.compile(r"^FD(\d+)JUMP(\d+)$")
+
+
+def fdjump_base(name: str) -> Optional[str]:
+    """The base name FD{p}JUMP of a par-file line spelt FD{p}JUMP or FDJUMP{p} (None: neither)."""
+    if re.match(r"^FD\d+JUMP$", name):
+        return name
+    m = re.match(r"^FDJUMP(\d+)$", name)
+    return f"FD{int(m.group(1))}JUMP" if m else None
+
 
 IGNORED = {"MODE", "NITS", "IBOOT", "RM", "SWP", "DMXEP", "DMXF1", "DMXF2"}
 

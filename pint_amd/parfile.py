@@ -34,6 +34,9 @@ A model with WaveX or DMWaveX writes the component's epoch, then ``FREQ_ SIN_ CO
 harmonic in parameter order (harmonic 0001, which the component always has, first), after the
 binary's lines; a frequency line carries no fit flag.  ChromaticCM writes CM, CM1, ..., then
 CMEPOCH and TNCHROMIDX (``chromatic_model.py:237-248``); CMWaveX follows it, written like DMWaveX.
+FDJump writes FDJUMPLOG and then its masks as ``FD{p}JUMP`` lines in parameter order, whichever
+spelling they were read in (``fdjump.py:195-206``: only the tempo2 format writes ``FDJUMP{p}``);
+FDJumpDM's ``FDJUMPDM`` lines follow.
 """
 from __future__ import annotations
 
@@ -248,7 +251,7 @@ _ORDER = {
     "PLDMNoise": ["TNDMAMP", "TNDMGAM", "TNDMC"],
 }
 MIDDLE = ["TroposphereDelay", "SolarSystemShapiro", "SolarWindDispersion", "DispersionDM", "DispersionDMX",
-          "Binary", "FD", "WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise",
+          "Binary", "FD", "WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise",
           "ScaleToaError", "PLRedNoise", "PLDMNoise"]
 
 

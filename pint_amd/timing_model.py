@@ -22,7 +22,7 @@ from .parameter import LD, Param
 # components supported on the hot path
 DELAY_ORDER = ["AstrometryEquatorial", "AstrometryEcliptic", "TroposphereDelay", "SolarSystemShapiro",
                "SolarWindDispersion", "DispersionDM", "DispersionDMX", "BinaryELL1", "BinaryDD", "FD", "WaveX",
-               "DMWaveX", "ChromaticCM", "CMWaveX"]
+               "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM"]
 PHASE_ORDER = ["AbsPhase", "Spindown", "Glitch", "PhaseOffset", "PhaseJump"]
 NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
 
@@ -39,6 +39,8 @@ GLITCH_DECLARED = ("GLPH_", "GLEP_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_
 # the reference DMWaveX, ChromaticCM and CMWaveX follow everything else in the order its model
 # builder adds them (a set's iteration order: it changes with the hash seed).  Here the order is
 # always ... binary, WaveX, DMWaveX, ChromaticCM, CMWaveX, for the delays and for the parameters.
+# FDJump (category fdjump) and FDJumpDM (fdjumpdm) are not in DEFAULT_ORDER either and follow in the
+# same seed-dependent way; here always ... CMWaveX, FDJump, FDJumpDM.
 WAVEX_STEMS = {"WaveX": "WX", "DMWaveX": "DMWX", "CMWaveX": "CMWX"}
 
 ELL1_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "EDOT", "OMDOT", "M2", "SINI", "TASC", "EPS1", "EPS2",
@@ -280,6 +282,24 @@ class TimingModel:
     def remove_cmwavex_component(self, index):
         """CMWaveX.remove_cmwavex_component (cmwavex.py:254-276)."""
         self.remove_wavex_component(index, component="CMWaveX")
+
+    def fdjump_params(self) -> List[str]:
+        """FDJump's mask parameters FD{p}JUMP{q} in parameter order (fdjump.py:91-95 fdjumps, the
+        unset ones the reference's constructor declares left out)."""
+        return self._names_of("fdjump", lambda: [n for n, p in self._params.items()
+                                                 if p.kind == "mask" and p.component == "FDJump"])
+
+    def fdjumpdm_params(self) -> List[str]:
+        """FDJumpDM's mask parameters FDJUMPDM{q} in parameter order (dispersion_model.py:848-851)."""
+        return self.mask_params("FDJUMPDM")
+
+    @staticmethod
+    def get_fd_index(par: str) -> int:
+        """FDJump.get_fd_index (fdjump.py:103-120): p of FD{p}JUMP{q}."""
+        m = P.FDJUMP_NAME.match(par)
+        if not m:
+            raise ValueError(f"The given parameter {par} does not correspond to an FDJUMP.")
+        return int(m.group(1))
 
     def glitch_indices(self) -> List[int]:
         """The glitch indices that appear in any GL*_n parameter, ascending (glitch.py:139-145)."""
@@ -566,6 +586,41 @@ def _parse_mask_line(model: TimingModel, base: str, fields: List[str], counters:
     return p
 
 
+def _parse_fdjump_lines(model: TimingModel, lines, counters: Dict[str, int]):
+    """FDJump's par lines (fdjump.py, model_builder._replace_fdjump_in_parfile_dict:80-99).  A line
+    is spelt FD{p}JUMP or, as tempo2 does, FDJUMP{p}; the reference renames the second spelling's
+    key in its dictionary of par lines, so when both spellings of one p occur the lines of the
+    spelling that appears later in the file replace the other's (recorded in fdj_wls.json
+    "forms").  p outside 1..20 is no parameter: the rewritten line is reported as unrecognised.
+    The component has FDJUMPLOG (Y) first, then FD{p}JUMP1 of every p in ascending p, then the
+    further masks of each p in the order of the lines."""
+    import warnings
+    groups: Dict[str, Dict[str, list]] = {}  # base -> spelling -> its lines (both in order of first appearance)
+    for l in lines:
+        base = P.fdjump_base(l.name)
+        if base is not None:
+            groups.setdefault(base, {}).setdefault(l.name, []).append(l)
+    if not groups and not any(l.name == "FDJUMPLOG" for l in lines):
+        return
+    p = P.make_param("FDJUMPLOG")  # (fdjump.py:69-75: the constructor's value)
+    p.value = True
+    model.add_param(p)
+    kept = []
+    for base, spell in groups.items():
+        ls = list(spell.values())[-1]
+        if base not in P.MASK_PARAMS:
+            for l in ls:
+                warnings.warn(f"Unrecognized parfile line '{' '.join([base] + l.fields)}'")
+            continue
+        kept.append((base, ls))
+    first = sorted(kept, key=lambda g: int(P.fdjump_base(g[0])[2:-4]))
+    for base, ls in first:
+        _parse_mask_line(model, base, ls[0].fields, counters)
+    for base, ls in kept:
+        for l in ls[1:]:
+            _parse_mask_line(model, base, l.fields, counters)
+
+
 def get_model(parfile) -> TimingModel:
     """Build a TimingModel from a par file (model_builder.py:777 get_model)."""
     lines = P.read_parfile(parfile)
@@ -636,9 +691,12 @@ def get_model(parfile) -> TimingModel:
                 model.add_param(p)
         if any(re.match(rf"^{stem}(EPOCH|(FREQ|SIN|COS)_\d{{4}})$", n) for n in names):
             model._ensure_wavex(comp)
+    _parse_fdjump_lines(model, lines, counters)
     for l in lines:
         raw = l.name
         name = P._ALIASES.get(raw, raw)
+        if P.fdjump_base(raw) is not None:  # (_parse_fdjump_lines)
+            continue
         if name in P.IGNORED or re.match(r"^DMX(EP|F1|F2)_\d+$", name):
             continue
         if name in P.MASK_PARAMS or raw in ("T2EFAC", "T2EQUAD", "TNECORR"):
