@@ -143,17 +143,38 @@ enum {
     PINT_GL_NPAR
 };
 /* binary parameter ids (stand_alone_psr_binaries/binary_generic.py, ELL1_model.py, DD_model.py,
- * ELL1H_model.py (H3, H4, STIGMA), DDK_model.py (KIN, KOM)) */
+ * ELL1H_model.py (H3, H4, STIGMA), DDK_model.py (KIN, KOM), DDS_model.py (SHAPMAX), DDH_model.py (H3,
+ * STIGMA), ELL1k_model.py (OMDOT, LNEDOT)) */
 enum {
     PINT_B_PB = 0, PINT_B_PBDOT, PINT_B_XPBDOT, PINT_B_A1, PINT_B_A1DOT, PINT_B_ECC,
     PINT_B_EDOT, PINT_B_T0, PINT_B_OM, PINT_B_OMDOT, PINT_B_M2, PINT_B_SINI, PINT_B_GAMMA,
     PINT_B_DR, PINT_B_DTH, PINT_B_A0, PINT_B_B0, PINT_B_TASC, PINT_B_EPS1, PINT_B_EPS2,
     PINT_B_EPS1DOT, PINT_B_EPS2DOT, PINT_B_H3, PINT_B_H4, PINT_B_STIGMA, PINT_B_KIN, PINT_B_KOM,
+    PINT_B_NPAR0,                        /* the length of spec.o_bin                                   */
+    PINT_B_SHAPMAX = PINT_B_NPAR0, PINT_B_LNEDOT,   /* their slots: PINT_SPEC_O_BINX(spec, id)          */
     PINT_B_NPAR
 };
-/* binary models (spec.binary) */
+/* binary models (spec.binary).
+ * dds (DDS_model.py): DD with SINI = 1 - exp(-SHAPMAX) wherever DD uses SINI; d SINI / d SHAPMAX =
+ *   exp(-SHAPMAX), no other parameter moves SINI.  SHAPMAX (dimensionless) must be > -log 2.
+ * ddh (DDH_model.py, Freire & Wex 2010): DD with SINI = 2 s / (1 + s^2) and T_sun M2 = H3 / s^3,
+ *   s = STIGMA > 0, H3 in s; the exact DD Shapiro delay -2 (H3 / s^3) log(logNum), not ELL1H's
+ *   harmonic sum.  d delayS / d H3 = -2 log(logNum) / s^3; d delayS / d STIGMA = 6 H3 / s^4
+ *   log(logNum) - 2 H3 / s^3 (-dSINI/ds X) / logNum, X = sin w (cos E - e) + sqrt(1 - e^2) cos w
+ *   sin E, dSINI/ds = 2 / (1 + s^2) - 4 s^2 / (1 + s^2)^2 (the reference's column carries a stray
+ *   1 / T_sun; this is the correct one).
+ * ell1k (ELL1k_model.py, Susobhanan et al. 2018): ELL1 without EPS1DOT / EPS2DOT / EDOT; with dt =
+ *   t - TASC, eps1 = (1 + LNEDOT dt)(EPS1 cos(OMDOT dt) + EPS2 sin(OMDOT dt)), eps2 = (1 + LNEDOT
+ *   dt)(EPS2 cos(OMDOT dt) - EPS1 sin(OMDOT dt)); OMDOT deg / yr, LNEDOT 1 / yr.  The Roemer delay
+ *   is the first-order a1 (sin Phi + (eps2 sin 2 Phi - eps1 (cos 2 Phi + 3)) / 2), with d Dre / d eps1
+ *   = -a1 (cos 2 Phi + 3) / 2 and d Dre / d eps2 = a1 sin 2 Phi / 2; Drep, Drepp, their partials and
+ *   the Shapiro delay are ELL1's.  d eps2 / d EPS2 = +d eps1 / d EPS1 (the reference has the
+ *   opposite sign; this is the correct one).
+ * A dds / ddh row whose Shapiro argument logNum is <= 0 sets PINT_E_KEPLER like a failed Kepler
+ * solve. */
 enum { PINT_BIN_NONE = 0, PINT_BIN_ELL1 = 1, PINT_BIN_DD = 2, PINT_BIN_ELL1H = 3, PINT_BIN_BT = 4, PINT_BIN_DDK = 5,
-       PINT_NBIN = 6 };
+       PINT_BIN_DDS = 6, PINT_BIN_DDH = 7, PINT_BIN_ELL1K = 8,
+       PINT_NBIN = 9 };
 
 typedef struct {
     int32_t nf;             /* spin terms F0..F{nf-1}                                   */
@@ -162,7 +183,8 @@ typedef struct {
                                PLANET_SHAPIRO planets (solar_system_shapiro.py:105-117)    */
     int32_t ndm;            /* DispersionDM taylor terms (0 = component absent)         */
     int32_t ndmx;           /* DMX bins                                                 */
-    int32_t binary;         /* PINT_BIN_*: 0 none, 1 ELL1, 2 DD, 3 ELL1H, 4 BT, 5 DDK   */
+    int32_t binary;         /* PINT_BIN_*: 0 none, 1 ELL1, 2 DD, 3 ELL1H, 4 BT, 5 DDK,
+                               6 DDS, 7 DDH, 8 ELL1k                                    */
     int32_t nfd;            /* FD terms                                                 */
     int32_t njump;          /* phase JUMPs                                              */
     int32_t track_pn;       /* 1: use_pulse_numbers, 0: nearest  (residuals.py:133-149) */
@@ -173,7 +195,7 @@ typedef struct {
     int32_t tstride;        /* doubles per instance parameter table                    */
     /* table offsets (doubles; each parameter is a dd pair at [off], [off+1]); -1 absent */
     int32_t o_F, o_PEPOCH, o_lon, o_lat, o_pmlon, o_pmlat, o_px, o_POSEPOCH;
-    int32_t o_DM, o_DMEPOCH, o_DMX, o_FD, o_JUMP, o_bin[PINT_B_NPAR];
+    int32_t o_DM, o_DMEPOCH, o_DMX, o_FD, o_JUMP, o_bin[PINT_B_NPAR0];
     int32_t o_PHOFF;        /* PhaseOffset: table slot of PHOFF (-1 none); the TOAs' phase gets
                                -PHOFF, the TZR TOA's does not (phase_offset.py offset_phase)    */
     int32_t wb_noones;      /* 1: the Woodbury chi2 has no offset column of ones (PHOFF free,
@@ -210,11 +232,18 @@ typedef struct {
                                registers no phase_derivs_wrt_delay (only spindown.py:85 does), so the
                                chain factor of the delay columns is unchanged                      */
     int32_t nglitch;        /* glitches (<= PINT_MAX_GLITCH), in ascending index                  */
-    int32_t rsv_[3];        /* unused reserve (keeps the header a whole number of 16-byte words)  */
+    int32_t rsv_[3];        /* rsv_[id - PINT_B_NPAR0] = 1 + the table slot of binary parameter id for
+                               the ids past o_bin (PINT_B_SHAPMAX, PINT_B_LNEDOT), 0 = absent: read
+                               with PINT_SPEC_O_BINX.  Kept in the reserve, biased by one, so that
+                               every field keeps its offset and a model without them keeps its spec
+                               bytes (all-zero reserve).  rsv_[2]: unused reserve (keeps the header a whole number of 16-byte words)  */
     int32_t col_kind[PINT_MAX_COLS];
     int32_t col_index[PINT_MAX_COLS];
     int32_t col_toff[PINT_MAX_COLS];  /* table offset of the column's parameter (-1: Offset) */
 } pint_spec_t;
+
+/* table slot of binary parameter id >= PINT_B_NPAR0 (-1 absent) */
+#define PINT_SPEC_O_BINX(spec, id) ((spec).rsv_[(id) - PINT_B_NPAR0] - 1)
 
 /* ---- context -------------------------------------------------------------------- */
 typedef struct pint_ctx pint_ctx;

@@ -471,6 +471,12 @@ PD double binp(const pint_spec_t& S, const double* P, int pid, double dflt = 0.0
     return o >= 0 ? pval(P, o) : dflt;
 }
 
+// the parameters past o_bin (PINT_B_SHAPMAX, PINT_B_LNEDOT: PINT_SPEC_O_BINX)
+PD double binpx(const pint_spec_t& S, const double* P, int pid) {
+    int o = PINT_SPEC_O_BINX(S, pid);
+    return o >= 0 ? pval(P, o) : 0.0;
+}
+
 // orbits (binary_orbits.py:98 OrbitPB.orbits) in dd; returns frac and floor
 PD void orbit_phase(dd tt0, dd ipbs, double pbdot_sum, BinState& B) {
     dd x = dd_mul(tt0, ipbs);  // tt0 / PB with the per-instance dd reciprocal
@@ -539,8 +545,13 @@ PD double ell1h_shapiro(const pint_spec_t& S, const double* P, BinState& B) {
     return H3 * B.hS_H3;
 }
 
-// ---- ELL1 (ELL1_model.py); H: ELL1H (binary_ell1.py:312, no M2/SINI, the H3 Shapiro delay)
-template <bool H>
+// ---- ELL1 (ELL1_model.py); H: ELL1H (binary_ell1.py:312, no M2/SINI, the H3 Shapiro delay);
+// KV: ELL1k (ELL1k_model.py, Susobhanan et al. 2018): eps1 / eps2 rotate with OMDOT and scale with
+// 1 + LNEDOT dt (:48-97), and the Roemer delay is the first-order form with the extra -3 a1 eps1 / 2
+// (:120-134); Drep, Drepp and the Shapiro delay stay ELL1's.  B.EPS1DOT / B.EPS2DOT then hold
+// d_eps1_d_EPS1 = (1 + LNEDOT dt) cos(OMDOT dt) and d_eps1_d_EPS2 = (1 + LNEDOT dt) sin(OMDOT dt),
+// B.EDOT LNEDOT (1/s), B.OMDOT_rs OMDOT (rad/s): the seeds of ell1k_deriv.
+template <bool H, bool KV = false>
 PD void ell1_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd tdb, double acc_delay, BinState& B) {
     dd tasc = pdd(P, S.o_bin[PINT_B_TASC]);
     // ttasc = (t - TASC) in s with t = tdbld*day - acc_delay (pulsar_binary.py:398, ELL1_model.py:42)
@@ -556,10 +567,23 @@ PD void ell1_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd
     B.pb = B.PBs + B.PBDOT * B.tt0;  // pbprime (binary_orbits.py:107)
     B.A1DOT = binp(S, P, PINT_B_A1DOT);
     B.a1 = binp(S, P, PINT_B_A1) + B.tt0 * B.A1DOT;
-    B.EPS1DOT = binp(S, P, PINT_B_EPS1DOT) * 1e-12;  // par units 1e-12/s -> 1/s
-    B.EPS2DOT = binp(S, P, PINT_B_EPS2DOT) * 1e-12;
-    B.eps1 = binp(S, P, PINT_B_EPS1) + B.tt0 * B.EPS1DOT;
-    B.eps2 = binp(S, P, PINT_B_EPS2) + B.tt0 * B.EPS2DOT;
+    if (KV) {
+        B.OMDOT_rs = binp(S, P, PINT_B_OMDOT) * (DEG_RAD / YR_S);
+        B.EDOT = binpx(S, P, PINT_B_LNEDOT) * (1.0 / YR_S);
+        double so, co;
+        sincos(B.OMDOT_rs * B.tt0, &so, &co);
+        const double g = 1.0 + B.EDOT * B.tt0;
+        const double E1 = binp(S, P, PINT_B_EPS1), E2 = binp(S, P, PINT_B_EPS2);
+        B.EPS1DOT = g * co;
+        B.EPS2DOT = g * so;
+        B.eps1 = g * (E1 * co + E2 * so);
+        B.eps2 = g * (E2 * co - E1 * so);
+    } else {
+        B.EPS1DOT = binp(S, P, PINT_B_EPS1DOT) * 1e-12;  // par units 1e-12/s -> 1/s
+        B.EPS2DOT = binp(S, P, PINT_B_EPS2DOT) * 1e-12;
+        B.eps1 = binp(S, P, PINT_B_EPS1) + B.tt0 * B.EPS1DOT;
+        B.eps2 = binp(S, P, PINT_B_EPS2) + B.tt0 * B.EPS2DOT;
+    }
     B.TM2 = H ? 0.0 : binp(S, P, PINT_B_M2) * TSUN;
     B.SINI = H ? 0.0 : binp(S, P, PINT_B_SINI);
     double Phi = B.Phi, e1 = B.eps1, e2 = B.eps2;
@@ -587,6 +611,7 @@ PD void ell1_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd
            (1.0 / 8) * (-5 * e2s * s1 + 27 * e2s * s3 + 2 * e1 * e2 * c1 - 54 * e1 * e2 * c3 - 3 * e1s * s1 - 27 * e1s * s3) -
            (1.0 / 12) * (-20 * e2s * e2 * s2 - 12 * e1s * e2 * s2 + 24 * e1 * e2s * c2 + 16 * e1s * e1 * c2 +
                          64 * e2s * e2 * s4 - 192 * e1s * e2 * s4 - 192 * e1 * e2s * c4 + 64 * e1s * e1 * c4);
+    if (KV) B.R0 = s1 + 0.5 * (e2 * s2 - e1 * (c2 + 3.0));  // ELL1k delayR (ELL1k_model.py:120-134)
     B.Dre = B.a1 * B.R0;  // delayR (:317)
     B.Drep = B.a1 * B.R1;  // Drep (:398)
     B.Drepp = B.a1 * B.R2;  // Drepp (:478)
@@ -616,7 +641,7 @@ struct Ell1Grad {
     double a1, Phi, e1, e2, pb, TM2, SINI;
 };
 
-template <bool H>
+template <bool H, bool KV = false>
 PD void ell1_grad(const BinState& B, Ell1Grad& g) {
     double e1 = B.eps1, e2 = B.eps2, a1 = B.a1;
     double s1 = B.s1, c1 = B.c1, s2 = B.s2, c2 = B.c2, s3 = B.s3, c3 = B.c3, s4 = B.s4, c4 = B.c4;
@@ -629,6 +654,10 @@ PD void ell1_grad(const BinState& B, Ell1Grad& g) {
     double dDre_de2 = a1 * (0.5 * s2 - (1.0 / 8) * (-2 * e1 * c1 + 6 * e1 * c3 + 10 * e2 * s1 - 6 * e2 * s3) -
                             (1.0 / 12) * (15 * e2s * s2 + 3 * e1s * s2 - 12 * e1 * e2 * c2 - 12 * e2s * s4 +
                                           12 * e1s * s4 + 24 * e1 * e2 * c4));
+    if (KV) {  // ELL1k d_Dre_d_par (ELL1k_model.py:136-170)
+        dDre_de1 = -0.5 * a1 * (c2 + 3.0);
+        dDre_de2 = 0.5 * a1 * s2;
+    }
     // d_Drep_d_par (:406-476)
     double dDrep_de1 = a1 * (s2 - (1.0 / 8) * (6 * e1 * c1 + 18 * e1 * c3 + 2 * e2 * s1 - 18 * e2 * s3) -
                              (1.0 / 12) * (12 * e1 * e2 * c2 + 12 * e2s * s2 + 16 * e1s * s2 + 96 * e1 * e2 * c4 -
@@ -689,6 +718,28 @@ PD double ell1_deriv(const BinState& B, const Ell1Grad& g, int pid) {
         case PINT_B_H4: return B.hS_sig * B.dsig_dH4;
         case PINT_B_STIGMA: return B.hS_sig;
         default: return 0.0;
+    }
+}
+
+// ELL1k's columns: ell1_deriv's dot products with the seeds of ELL1k_model.py:60-118 for EPS1, EPS2,
+// OMDOT, LNEDOT and TASC.  d_eps2_d_EPS2 = +d_eps1_d_EPS1: the reference returns the negative
+// (:102-103), which disagrees with its own numerical derivative and keeps its fitters from
+// converging with EPS2 free.
+PD double ell1k_deriv(const BinState& B, const Ell1Grad& g, int pid) {
+    const double tt0 = B.tt0, ce = B.EPS1DOT, se = B.EPS2DOT;
+    switch (pid) {
+        case PINT_B_EPS1: return g.e1 * ce - g.e2 * se;
+        case PINT_B_EPS2: return g.e1 * se + g.e2 * ce;
+        case PINT_B_OMDOT: return (g.e1 * B.eps2 - g.e2 * B.eps1) * tt0;
+        case PINT_B_LNEDOT:  // per 1/yr, the par unit (binary_ell1.py:475-483): bin_unit_factor(), which
+            // every model's build shares, keeps its cases
+            return (g.e1 * B.eps1 + g.e2 * B.eps2) * tt0 / (1.0 + B.EDOT * tt0) * (1.0 / YR_S);
+        case PINT_B_TASC: {
+            const double l = B.EDOT / (1.0 + B.EDOT * tt0);
+            return g.e1 * (-B.eps1 * l - B.eps2 * B.OMDOT_rs) + g.e2 * (-B.eps2 * l + B.eps1 * B.OMDOT_rs) +
+                   g.Phi * ((B.PBDOT * tt0 * B.ipb - 1.0) * TWO_PI * B.ipb);
+        }
+        default: return ell1_deriv(B, g, pid);
     }
 }
 
@@ -754,7 +805,13 @@ PD void ddk_kopeikin(const pint_spec_t& S, const double* P, const double obs[3],
 }
 
 // ---- DD (DD_model.py, binary_generic.py) ------------------------------------------
-template <bool K = false>
+// The variant V picks where the Shapiro delay's SINI and TM2 come from; everything else is shared.
+// DDS (DDS_model.py): SINI = 1 - exp(-SHAPMAX), B.kSI[0] = d SINI / d SHAPMAX = exp(-SHAPMAX).
+// DDH (DDH_model.py, Freire & Wex 2010): SINI = 2 s / (1 + s^2), TM2 = H3 / s^3 (s = STIGMA); B.kSI =
+// {d SINI / d s, d TM2 / d s, d TM2 / d H3}.  In both a row with logNum <= 0 (reachable: SINI is
+// not bounded by the par file here) sets PINT_E_KEPLER instead of a NaN delay.
+enum { DDV_DD = 0, DDV_DDK = 1, DDV_DDS = 2, DDV_DDH = 3 };
+template <int V = DDV_DD>
 PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd tdb, double acc_delay, BinState& B,
                   const double* kobs = nullptr, const double* kpsr = nullptr) {
     dd T0 = pdd(P, S.o_bin[PINT_B_T0]);
@@ -772,8 +829,23 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     B.a1 = binp(S, P, PINT_B_A1) + B.tt0 * B.A1DOT;
     B.EDOT = binp(S, P, PINT_B_EDOT);
     B.ecc = binp(S, P, PINT_B_ECC) + B.tt0 * B.EDOT;
-    B.TM2 = binp(S, P, PINT_B_M2) * TSUN;
-    B.SINI = binp(S, P, PINT_B_SINI);
+    if (V == DDV_DDH) {
+        const double sg = binp(S, P, PINT_B_STIGMA), H3 = binp(S, P, PINT_B_H3);
+        const double i1 = 1.0 / (1.0 + sg * sg), is = 1.0 / sg, is3 = is * is * is;
+        B.SINI = 2.0 * sg * i1;
+        B.TM2 = H3 * is3;
+        B.kSI[0] = 2.0 * i1 - 4.0 * sg * sg * i1 * i1;
+        B.kSI[1] = -3.0 * H3 * is3 * is;
+        B.kSI[2] = is3;
+    } else {
+        B.TM2 = binp(S, P, PINT_B_M2) * TSUN;
+        if (V == DDV_DDS) {
+            B.kSI[0] = exp(-binpx(S, P, PINT_B_SHAPMAX));
+            B.SINI = 1.0 - B.kSI[0];
+        } else {
+            B.SINI = binp(S, P, PINT_B_SINI);
+        }
+    }
     B.GAMMA = binp(S, P, PINT_B_GAMMA);
     B.DR = binp(S, P, PINT_B_DR);
     B.DTH = binp(S, P, PINT_B_DTH);
@@ -805,7 +877,7 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     B.ipb = 1.0 / B.pb;
     B.k = B.OMDOT_rs * B.pb * INV_TWO_PI;             // DD_model.py:76 k
     B.omega = binp(S, P, PINT_B_OM) * DEG_RAD + B.nu * B.k;  // :86
-    if (K) ddk_kopeikin(S, P, kobs, kpsr, B);
+    if (V == DDV_DDK) ddk_kopeikin(S, P, kobs, kpsr, B);
     B.er = e * (1 + B.DR);
     B.eTheta = e * (1 + B.DTH);
     double sw, cw;
@@ -831,6 +903,10 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     double delayI = B.Dre * (1 - nH * B.Drep + (nH * B.Drep) * (nH * B.Drep) + 0.5 * nH * nH * B.Dre * B.Drepp -
                              0.5 * e * sE * B.iomeE * nH * nH * B.Dre * B.Drep);  // :602-646
     double logNum = 1 - e * cE - B.SINI * (sw * (cE - e) + B.sqE * cw * sE);
+    if ((V == DDV_DDS || V == DDV_DDH) && !(logNum > 0.0)) {  // (NaN too: a non-finite STIGMA or SHAPMAX)
+        B.status = PINT_E_KEPLER;
+        logNum = 1.0;
+    }
     B.logNum = logNum;
     B.lgNum = log(logNum);
     B.ilogNum = 1.0 / logNum;
@@ -841,7 +917,7 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     B.delay = delayI + delayS + delayA;
 }
 
-template <bool K = false>
+template <int V = DDV_DD>
 PD double ddm_deriv(const BinState& B, int pid) {
     const double e = B.ecc, sE = B.sinE, cE = B.cosE, tt0 = B.tt0;
     const double iP = B.iPBs, iP2 = iP * iP;
@@ -865,7 +941,9 @@ PD double ddm_deriv(const BinState& B, int pid) {
     }
     // DDK: Kopeikin pieces of d_a1_d_par / d_omega_d_par / prtl_der("SINI", .)
     double k_a1 = 0.0, k_om = 0.0, k_si = (pid == PINT_B_SINI) ? 1.0 : 0.0;
-    if (K) {
+    if (V == DDV_DDS) k_si = (pid == PINT_B_SHAPMAX) ? B.kSI[0] : 0.0;
+    if (V == DDV_DDH) k_si = (pid == PINT_B_STIGMA) ? B.kSI[0] : 0.0;
+    if (V == DDV_DDK) {
         const int j = pid == PINT_B_KIN ? 0 : (pid == PINT_B_KOM ? 1 : (pid == PINT_B_T0 ? 2 : -1));
         k_si = 0.0;
         if (j >= 0) {
@@ -942,6 +1020,9 @@ PD double ddm_deriv(const BinState& B, int pid) {
     double sq1 = B.sqE;
     double ilN = B.ilogNum;
     double d_TM2 = (pid == PINT_B_M2) ? TSUN : 0.0;
+    // DDH (DDH_model.py:85-160): through TM2 = H3 / s^3 and SINI(s); the reference's STIGMA column
+    // carries a stray 1 / Tsun in both terms, this is the derivative itself
+    if (V == DDV_DDH) d_TM2 = (pid == PINT_B_STIGMA) ? B.kSI[1] : ((pid == PINT_B_H3) ? B.kSI[2] : 0.0);
     double d_SINI = k_si;
     double TM2 = B.TM2;
     double dS = d_TM2 * (-2 * B.lgNum) +
@@ -1474,8 +1555,15 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
     if (BIN == 1 || BIN == 3) {
         ell1_setup<BIN == 3>(S, P, C, t.tdb, delay, B);
         delay += B.delay;
+    } else if (BIN == 8) {
+        ell1_setup<false, true>(S, P, C, t.tdb, delay, B);
+        delay += B.delay;
     } else if (BIN == 2) {
         ddm_setup(S, P, C, t.tdb, delay, B);
+        delay += B.delay;
+        if (B.status) o.status = B.status;
+    } else if (BIN == 6 || BIN == 7) {
+        ddm_setup<BIN == 6 ? DDV_DDS : DDV_DDH>(S, P, C, t.tdb, delay, B);
         delay += B.delay;
         if (B.status) o.status = B.status;
     } else if (BIN == 4) {
@@ -1489,7 +1577,7 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
             icrs_to_ecl(S.obliquity, t.pos, ko);
             icrs_to_ecl(S.obliquity, L, kp);
         }
-        ddm_setup<true>(S, P, C, t.tdb, delay, B, ko, kp);
+        ddm_setup<DDV_DDK>(S, P, C, t.tdb, delay, B, ko, kp);
         delay += B.delay;
         if (B.status) o.status = B.status;
     }
@@ -1502,6 +1590,7 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
     if (Mb && BIN != 0) {
         Ell1Grad eg;
         if (BIN == 1 || BIN == 3) ell1_grad<BIN == 3>(B, eg);
+        if (BIN == 8) ell1_grad<false, true>(B, eg);
         for (int u = 0; u < nrun; u++) {
             const ColRun R = runs[u];
             if (R.kind != PINT_COL_BIN) continue;
@@ -1512,7 +1601,10 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
                 if (BIN == 1 || BIN == 3) d = ell1_deriv(B, eg, pid);
                 if (BIN == 2) d = ddm_deriv(B, pid);
                 if (BIN == 4) d = bt_deriv(B, pid);
-                if (BIN == 5) d = ddm_deriv<true>(B, pid);
+                if (BIN == 5) d = ddm_deriv<DDV_DDK>(B, pid);
+                if (BIN == 6) d = ddm_deriv<DDV_DDS>(B, pid);
+                if (BIN == 7) d = ddm_deriv<DDV_DDH>(B, pid);
+                if (BIN == 8) d = ell1k_deriv(B, eg, pid);
                 colp[r] = chain * d * bin_unit_factor(pid);
             }
         }

@@ -6901,7 +6901,7 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
         ctx->err = "bad glitch count or table slot (PINT_MAX_GLITCH)";
         return -PINT_E_INVALID;
     }
-    if (spec->binary < 0 || spec->binary > PINT_BIN_DDK) { ctx->err = "unsupported binary model"; return -PINT_E_INVALID; }
+    if (spec->binary < 0 || spec->binary >= PINT_NBIN) { ctx->err = "unsupported binary model"; return -PINT_E_INVALID; }
     if (spec->binary == PINT_BIN_ELL1H &&
         (spec->ell1h < 1 || spec->ell1h > 3 || (spec->ell1h == 2 && (spec->nharms < 3 || spec->nharms > 64)))) {
         ctx->err = "bad ELL1H Shapiro form";
@@ -8129,7 +8129,7 @@ int pint_eval(pint_ctx* ctx, int want_M) {
         HIPCHK(hipGetLastError());
     }
     // one launch per binary model, back to back on the stream: all models without the merged
-    // launch; ELL1H/BT/DDK always (they stay out of k_eval_mix so its register set, which
+    // launch; ELL1H/BT/DDK/DDS/DDH/ELL1k always (they stay out of k_eval_mix so its register set, which
     // every block of the merged launch carries, is not raised by the rarer models)
     for (int t = spin_pass ? PINT_NBIN : (mix ? 3 : 0); t < PINT_NBIN; t++) {
         int nb = ctx->blk_off[t + 1] - ctx->blk_off[t];
@@ -8157,7 +8157,10 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                 case 2: PINT_EVAL_LAUNCH(1, 2); break;
                 case 3: PINT_EVAL_LAUNCH(1, 3); break;
                 case 4: PINT_EVAL_LAUNCH(1, 4); break;
-                default: PINT_EVAL_LAUNCH(1, 5); break;
+                case 5: PINT_EVAL_LAUNCH(1, 5); break;
+                case 6: PINT_EVAL_LAUNCH(1, 6); break;
+                case 7: PINT_EVAL_LAUNCH(1, 7); break;
+                default: PINT_EVAL_LAUNCH(1, 8); break;
             }
         } else {
             switch (t) {
@@ -8166,7 +8169,10 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                 case 2: PINT_EVAL_LAUNCH(0, 2); break;
                 case 3: PINT_EVAL_LAUNCH(0, 3); break;
                 case 4: PINT_EVAL_LAUNCH(0, 4); break;
-                default: PINT_EVAL_LAUNCH(0, 5); break;
+                case 5: PINT_EVAL_LAUNCH(0, 5); break;
+                case 6: PINT_EVAL_LAUNCH(0, 6); break;
+                case 7: PINT_EVAL_LAUNCH(0, 7); break;
+                default: PINT_EVAL_LAUNCH(0, 8); break;
             }
         }
 #undef PINT_EVAL_LAUNCH

@@ -244,12 +244,15 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         fdj_desc = (starts[0], len(fdjs), np.array([model.get_fd_index(n) for n in fdjs] or [0], dtype=np.int32),
                     use_log, masks[0], starts[1], len(fdjdms), masks[1])
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
-                   "DDK": L.BIN_DDK}[model.binary]
+                   "DDK": L.BIN_DDK, "DDS": L.BIN_DDS, "DDH": L.BIN_DDH, "ELL1k": L.BIN_ELL1K}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
     if model.binary:
         for n, pid in BIN_IDS.items():
-            if n in model:
-                spec.o_bin[pid] = place(n)
+            if n in model and model[n].kind != "func":  # (DDS's SINI, DDH's SINI / M2: derived on the device)
+                if pid < L.B_NPAR:
+                    spec.o_bin[pid] = place(n)
+                else:  # (SHAPMAX, LNEDOT: PINT_SPEC_O_BINX, 1 + the slot in the reserve)
+                    spec.rsv_[pid - L.B_NPAR] = 1 + place(n)
         if model.binary == "ELL1H":
             # BinaryELL1H.setup (binary_ell1.py:383-405)
             has4 = model.H4.value is not None
@@ -263,7 +266,10 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
                 raise ValueError("To use H4, H3 needs to be significant(H3 != 0).")
             spec.ell1h = 2 if has4 else (3 if hasst else 1)
             spec.nharms = max(int(nh), 7) if (has4 and nh is not None) else (7 if has4 else int(nh or 3))
-        need = ["PB", "A1", "TASC" if model.binary in ("ELL1", "ELL1H") else "T0"]
+        if model.binary == "DDH" and not (model.STIGMA.value is not None and float(model.STIGMA.value) > 0):
+            # (the reference divides by STIGMA^3 and goes on with inf or a TypeError)
+            raise ValueError(f"DDH needs STIGMA > 0 (STIGMA is {model.STIGMA.value}): M2 = H3 / STIGMA^3")
+        need = ["PB", "A1", "TASC" if model.binary in ("ELL1", "ELL1H", "ELL1k") else "T0"]
         for n in need:
             if n not in model or model[n].value is None:
                 raise ValueError(f"binary parameter {n} missing")

@@ -131,6 +131,43 @@ class Param:
         return f"{self.name} ({self.units}) {self.value} frozen={self.frozen}"
 
 
+class FuncParam(Param):
+    """The reference's funcParameter (parameter.py:2390): a value computed from other parameters
+    (DDS's SINI, DDH's SINI and M2).  Read-only and always frozen: setting it does nothing, as in the
+    reference, and it is never written to a par file; None while an input is unset."""
+
+    def __init__(self, name, units, func, inputs, component="Binary"):
+        Param.__init__(self, name=name, kind="func", units=units, component=component)
+        object.__setattr__(self, "_func", func)
+        object.__setattr__(self, "_inputs", tuple(inputs))
+
+    def __setattr__(self, key, v):
+        if key not in ("value", "frozen", "uncertainty_value"):
+            object.__setattr__(self, key, v)
+
+    @property
+    def value(self):
+        args = [p.value for p in self._inputs]
+        if any(a is None for a in args):
+            return None
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self._func(*[np.float64(a) for a in args])
+
+    @property
+    def frozen(self):
+        return True
+
+    @property
+    def uncertainty_value(self):
+        return None
+
+    def set_from_string(self, s):
+        pass
+
+    def set_uncertainty_from_string(self, s):
+        pass
+
+
 # ---- parameter definitions -----------------------------------------------------------
 # name -> (component, kind, units, long_double, scale)
 _DEFS = {
@@ -202,6 +239,9 @@ _DEFS = {
     "KIN": ("Binary", "float", "deg", False, None), "KOM": ("Binary", "float", "deg", False, None),
     "K96": ("Binary", "bool", "", False, None),
     "A0": ("Binary", "float", "s", False, None), "B0": ("Binary", "float", "s", False, None),
+    # DDS (binary_dd.py:180-188): SINI = 1 - exp(-SHAPMAX); ELL1k (binary_ell1.py:475-483): EDOT / ECC
+    "SHAPMAX": ("Binary", "float", "", False, None),
+    "LNEDOT": ("Binary", "float", "1 / yr", True, None),
     "TASC": ("Binary", "mjd", "d", True, None),
     "EPS1": ("Binary", "float", "", True, None), "EPS2": ("Binary", "float", "", True, None),
     "EPS1DOT": ("Binary", "float", "1e-12 / s", True, None),

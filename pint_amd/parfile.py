@@ -206,7 +206,7 @@ def _display_name(p: Param) -> str:
 def parfile_line(p: Param) -> str:
     """The reference's as_parfile_line (parameter.py:441, :2039) for one parameter; "" when
     unset."""
-    if p.value is None:
+    if p.kind == "func" or p.value is None:  # (a funcParameter is a comment line in the reference)
         return ""
     if getattr(p, "implicit", False) and p.frozen and p.value == 0:
         return ""  # a default the reference leaves unset (None): not written
@@ -245,6 +245,11 @@ _ORDER = {
     "DDK": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "A0", "B0", "GAMMA",
             "DR", "DTH", "KIN", "KOM", "K96"],
     "BT": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "GAMMA"],
+    "DDS": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "A0", "B0", "GAMMA", "DR",
+            "DTH", "SHAPMAX"],
+    "DDH": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "A0", "B0", "GAMMA", "DR", "DTH",
+            "H3", "STIGMA"],
+    "ELL1k": ["PB", "PBDOT", "A1", "A1DOT", "M2", "SINI", "TASC", "EPS1", "EPS2", "OMDOT", "LNEDOT"],
     "ELL1H": ["PB", "PBDOT", "A1", "A1DOT", "TASC", "EPS1", "EPS2", "EPS1DOT", "EPS2DOT", "H3", "H4", "STIGMA",
               "NHARMS"],
     "PLRedNoise": ["RNAMP", "RNIDX", "TNREDAMP", "TNREDGAM", "TNREDC"],

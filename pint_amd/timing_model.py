@@ -48,11 +48,20 @@ ELL1_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "EDOT", "OMDOT", "M2", "SINI", "TAS
 DD_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "SINI", "A0", "B0",
              "GAMMA", "DR", "DTH"]
 DDK_PARAMS = [n for n in DD_PARAMS if n != "SINI"] + ["KIN", "KOM"]  # binary_ddk.py:120-145
+# DDS (binary_dd.py:173-198): DD with SHAPMAX in place of SINI, which stays readable as a derived
+# parameter; DDH (:409-452): H3 and STIGMA in place of M2 and SINI, both derived; ELL1k
+# (binary_ell1.py:455-483): ELL1 less EDOT / EPS1DOT / EPS2DOT, OMDOT re-declared after EPS2, LNEDOT.
+# Each in the order the reference's component holds its parameters.
+DDS_PARAMS = [n for n in DD_PARAMS if n != "SINI"] + ["SHAPMAX", "SINI"]
+DDH_PARAMS = [n for n in DD_PARAMS if n not in ("M2", "SINI")] + ["H3", "STIGMA", "SINI", "M2"]
+ELL1K_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "M2", "SINI", "TASC", "EPS1", "EPS2", "OMDOT", "LNEDOT"]
+ELL1K_REMOVED = ("EPS1DOT", "EPS2DOT", "EDOT")
+BINARIES = ("ELL1", "DD", "ELL1H", "BT", "DDK", "DDS", "DDH", "ELL1k")
 BT_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "GAMMA"]
 BIN_IDS = {"PB": 0, "PBDOT": 1, "XPBDOT": 2, "A1": 3, "A1DOT": 4, "ECC": 5, "EDOT": 6, "T0": 7, "OM": 8,
            "OMDOT": 9, "M2": 10, "SINI": 11, "GAMMA": 12, "DR": 13, "DTH": 14, "A0": 15, "B0": 16,
            "TASC": 17, "EPS1": 18, "EPS2": 19, "EPS1DOT": 20, "EPS2DOT": 21, "H3": 22, "H4": 23, "STIGMA": 24,
-           "KIN": 25, "KOM": 26}
+           "KIN": 25, "KOM": 26, "SHAPMAX": 27, "LNEDOT": 28}
 # obliquity values (rad) from the reference's runtime ecliptic.dat (pulsar_ecliptic.py:29)
 OBLIQUITY = {"IERS2010": 0.4090926006005829, "IERS2003": 0.40909260011576914,
              "DEFAULT": 84381.406 / 206264.80624709636}
@@ -64,6 +73,28 @@ class MissingParameter(ValueError):
 
 class TimingModelError(ValueError):
     """timing_model.py TimingModelError (an invalid model structure)."""
+
+
+class UnknownBinaryModel(TimingModelError):
+    """timing_model.py UnknownBinaryModel (a BINARY line that names no model)."""
+
+
+def _sini_from_shapmax(shapmax):
+    """binary_dd.py:18 (DDS)."""
+    return 1.0 - np.exp(-shapmax)
+
+
+def _sini_from_stigma(stigma):
+    """binary_dd.py:30 (DDH, Freire & Wex 2010 Eq. 12)."""
+    return 2.0 * stigma / (1.0 + stigma ** 2)
+
+
+def _m2_from_h3_stigma(h3, stigma):
+    """binary_dd.py:26 (DDH): H3 / STIGMA^3 / T_sun, in solar masses."""
+    return h3 / stigma ** 3 / TSUN_S
+
+
+TSUN_S = 4.92549094830932e-06  # G M_sun / c^3 (s), the reference's Tsun (pint/__init__.py:80)
 
 
 class TimingModel:
@@ -473,10 +504,13 @@ class TimingModel:
         if "CMWaveX" in self.components and "ChromaticCM" not in self.components:
             # (the reference fails only when the delay is first evaluated, with a KeyError on TNCHROMIDX)
             raise TimingModelError("CMWaveX needs a ChromaticCM component (its TNCHROMIDX is the chromatic index)")
-        if self.binary in ("DD", "BT", "DDK"):
+        if self.binary in ("DD", "BT", "DDK", "DDS", "DDH"):
             e = float(self.ECC.value or 0.0)
             if not (0 <= e < 1):
                 raise ValueError("Eccentricity should be in the range of [0,1).")
+        if self.binary == "DDS" and self.SHAPMAX.value is not None and not self.SHAPMAX.value > -np.log(2):
+            # BinaryDDS.validate (binary_dd.py:200-208)
+            raise ValueError(f"SHAPMAX must be > -log(2) ({self.SHAPMAX.value})")
         if self.binary == "DDK":  # BinaryDDK.validate (binary_ddk.py:200-231)
             if not self.astrometry_kind:
                 raise TimingModelError("No valid AstrometryEcliptic or AstrometryEquatorial component found")
@@ -630,9 +664,13 @@ def get_model(parfile) -> TimingModel:
     binary = None
     for l in lines:
         if l.name == "BINARY" and l.fields:
-            binary = l.fields[0].upper()
-    if binary not in (None, "ELL1", "DD", "ELL1H", "BT", "DDK"):
-        raise NotImplementedError(f"BINARY {binary} is outside the supported hot path (ELL1, ELL1H, DD, DDK, BT)")
+            # (the reference's component names are case-sensitive: ELL1k, not ELL1K; the other
+            # names are all upper case and were always matched after upper())
+            binary = l.fields[0] if l.fields[0] == "ELL1k" else l.fields[0].upper()
+    if binary == "ELL1K":
+        raise UnknownBinaryModel("Pulsar system/Binary model component ELL1K is not provided. Perhaps use ELL1k?")
+    if binary not in (None,) + BINARIES:
+        raise NotImplementedError(f"BINARY {binary} is outside the supported hot path ({', '.join(BINARIES)})")
     model.binary = binary
     has_eq = any(n in ("RAJ", "RA") for n in names)
     has_ecl = any(n in ("ELONG", "LAMBDA") for n in names)
@@ -664,6 +702,15 @@ def get_model(parfile) -> TimingModel:
     elif binary == "DDK":  # DD's parameters less SINI, KIN/KOM 0, K96 unset (default True)
         defaults += [(n, 0.0) for n in DDK_PARAMS]
         defaults += [("T0", None), ("K96", None)]
+    elif binary == "DDS":  # SHAPMAX 0 as constructed (binary_dd.py:180-188)
+        defaults += [(n, 0.0) for n in DDS_PARAMS if n != "SINI"]
+        defaults += [("T0", None)]
+    elif binary == "DDH":  # H3 and STIGMA unset (binary_dd.py:414-432)
+        defaults += [(n, 0.0 if n not in ("H3", "STIGMA") else None) for n in DDH_PARAMS if n not in ("SINI", "M2")]
+        defaults += [("T0", None)]
+    elif binary == "ELL1k":  # OMDOT and LNEDOT unset (binary_ell1.py:465-483)
+        defaults += [(n, 0.0) for n in ELL1K_PARAMS]
+        defaults += [("TASC", None)]
     elif binary == "BT":  # binary_bt.py:38-69: no M2/SINI, GAMMA 0, rates 0
         defaults += [(n, 0.0) for n in BT_PARAMS if n != "T0"]
         defaults += [("T0", None)]
@@ -677,10 +724,17 @@ def get_model(parfile) -> TimingModel:
             v = LD(v)
         p.value = v
         # ELL1's rates are unset (None) in the reference (binary_ell1.py), 0 here
-        p.implicit = binary in ("ELL1", "ELL1H") and n in ("PBDOT", "A1DOT", "EDOT", "OMDOT", "EPS1DOT", "EPS2DOT")
+        p.implicit = binary in ("ELL1", "ELL1H", "ELL1k") and n in ("PBDOT", "A1DOT", "EDOT", "OMDOT", "EPS1DOT",
+                                                                    "EPS2DOT", "LNEDOT")
         if p.component == "Binary":
             p.component = "Binary"
         model.add_param(p)
+    # the derived parameters, where the reference's constructor adds them (after SHAPMAX / STIGMA)
+    if binary == "DDS":
+        model.add_param(P.FuncParam("SINI", "", _sini_from_shapmax, [model["SHAPMAX"]]))
+    elif binary == "DDH":
+        model.add_param(P.FuncParam("SINI", "", _sini_from_stigma, [model["STIGMA"]]))
+        model.add_param(P.FuncParam("M2", "solMass", _m2_from_h3_stigma, [model["H3"], model["STIGMA"]]))
     # WaveX, DMWaveX, ChromaticCM, then CMWaveX, after the binary's parameters (the components as
     # constructed; ChromaticCM, chromatic_model.py:128-169: CM 0, CM1 unset, CMEPOCH unset, TNCHROMIDX 4)
     for comp, stem in WAVEX_STEMS.items():
@@ -711,6 +765,11 @@ def get_model(parfile) -> TimingModel:
             if "BINARY" not in model:
                 model.add_param(p)
             continue
+        if binary == "ELL1k" and name in ELL1K_REMOVED:
+            # (BinaryELL1k removes them, binary_ell1.py:460-463; the reference's model builder then
+            # refuses the line, ell1k_wls.json "forms")
+            raise TimingModelError(f"Parameter {name} is recognized, but not used in the current timing model "
+                                   "(BinaryELL1k has OMDOT and LNEDOT in place of EPS1DOT, EPS2DOT and EDOT).")
         if name not in model:
             p = P.make_param(name)
             if p is None:
