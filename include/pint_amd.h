@@ -575,7 +575,36 @@ int pint_graph_launch(pint_ctx *ctx);
 #define PINT_QUERY_NVGRAM 1
 #define PINT_QUERY_NSPLIT 2
 #define PINT_QUERY_NSPINEVAL 3
+#define PINT_QUERY_WFUSE 4      /* 1: the batch's residual pass forms the post-fit Woodbury dots (k_resid2
+                                   tiles): every noise basis a PLRedNoise series of at most 63 modes */
 int pint_query(pint_ctx *ctx, int key);
+/* The launch plan of the last pint_fit_step (host bookkeeping, no reference counterpart): which
+ * kernel instantiations the call enqueued, as the dispatcher chose them from the batch's padded
+ * widths.  The tests assert it, so that a case written for one instantiation cannot stop
+ * exercising it unnoticed when a threshold moves.  A pint_fit_step that refuses its batch
+ * (PINT_E_INVALID before any launch) leaves an all-zero plan. */
+#define PINT_PLAN_MAXVKEY 18
+enum { PINT_PLAN_SOLVE_NONE = 0, PINT_PLAN_SOLVE_LANES4, PINT_PLAN_SOLVE_LANES8, PINT_PLAN_SOLVE_BLK1,
+       PINT_PLAN_SOLVE_BLK4, PINT_PLAN_SOLVE_BLK16, PINT_PLAN_SOLVE_COLUMN };
+typedef struct {
+    int32_t gram_t_mask;    /* bit T: k_gram<T> launched (T = 1..9 upper tiles per wave)          */
+    int32_t gram_ecorr;     /* the ECORR variants k_gram<T, ch, true> ran                        */
+    int32_t gram_s;         /* k_gram_s ran                                                      */
+    int32_t nvkey;          /* k_gram_v launches; vkey[i] = 10 (R - 1) + C, vkey_vb[i] the vb body */
+    int32_t vkey[PINT_PLAN_MAXVKEY];
+    int32_t vkey_vb[PINT_PLAN_MAXVKEY];
+    int32_t nsplit;         /* Gram row blocks per instance                                      */
+    int32_t greduce, dmx_rows, dmx, ecorr_dmx, wb_gram;  /* k_greduce, k_dmx_rows, k_dmx, k_ecorr_dmx, k_wb_gram ran */
+    int32_t solve;          /* PINT_PLAN_SOLVE_*: the general solve kernel                       */
+    int32_t solve_dmx_waves;/* k_solve_dmx<NW>: 0 (not launched), 8 or 16                        */
+    int32_t fuse_sigma;     /* Woodbury Sigma factored in k_solve_dmx's grid                     */
+    int32_t side_sigma;     /* ... by k_sigma on the side stream                                 */
+    int32_t do_sigma;       /* ... inside k_solve                                                */
+    int32_t sigma_waves;    /* k_sigma<NW>: 0, 4 or 16                                           */
+    int32_t schur;          /* k_schur ran in front of k_solve_dmx                               */
+    int32_t cov_deferred;   /* the covariance is left to k_cov_dmx at the read                   */
+} pint_plan_t;
+int pint_last_plan(pint_ctx *ctx, pint_plan_t *out);
 /* Page-locked host memory for the output buffers (hipHostMalloc); NULL on failure. */
 void *pint_host_alloc(size_t bytes);
 void pint_host_free(void *p);

@@ -57,6 +57,19 @@ class SpecT(C.Structure):
         ("col_kind", C.c_int32 * MAX_COLS), ("col_index", C.c_int32 * MAX_COLS), ("col_toff", C.c_int32 * MAX_COLS)]
 
 
+PLAN_MAXVKEY = 18  # PINT_PLAN_MAXVKEY
+PLAN_SOLVE = ("none", "lanes4", "lanes8", "blk1", "blk4", "blk16", "column")  # PINT_PLAN_SOLVE_*
+
+
+class PlanT(C.Structure):
+    """pint_plan_t: the launch plan of the last pint_fit_step."""
+    _fields_ = [("gram_t_mask", C.c_int32), ("gram_ecorr", C.c_int32), ("gram_s", C.c_int32), ("nvkey", C.c_int32),
+                ("vkey", C.c_int32 * PLAN_MAXVKEY), ("vkey_vb", C.c_int32 * PLAN_MAXVKEY)] + [
+        (n, C.c_int32) for n in ("nsplit", "greduce", "dmx_rows", "dmx", "ecorr_dmx", "wb_gram", "solve",
+                                 "solve_dmx_waves", "fuse_sigma", "side_sigma", "do_sigma", "sigma_waves", "schur",
+                                 "cov_deferred")]
+
+
 class PintError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"[pint_hip status {code}] {msg}")
@@ -158,6 +171,7 @@ def lib():
     for fn in ("pint_capture_begin", "pint_capture_end", "pint_graph_launch"):
         getattr(L, fn).argtypes = [vp]
     L.pint_query.restype = C.c_int
+    L.pint_last_plan.argtypes = [vp, C.POINTER(PlanT)]
     L.pint_fit_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
     L.pint_vgram_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
     L.pint_lognorm.argtypes = [vp, C.c_int, dptr]
@@ -203,7 +217,7 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_noise_lnlike", "pint_noise_resids_dm", "pint_set_wideband", "pint_dm_resids", "pint_chi2_wls",
             "pint_apply_step_uniform", "pint_fit_step_apply", "pint_save_tables", "pint_restore_tables", "pint_read_norms",
             "pint_fit_step_enqueue", "pint_set_grid", "pint_add_pulsar_cols", "pint_pack_toas",
-            "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump"]
+            "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

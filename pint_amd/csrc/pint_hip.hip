@@ -6026,6 +6026,7 @@ struct pint_ctx {
     int refine = 1;         // PINT_OPT_REFINE: iterative refinement of ill-conditioned solves
     int gvdbg = 0;          // (experiment) k_gram_v phases switched off
     int nsplit = 1;
+    pint_plan_t plan{};     // what the last pint_fit_step launched (pint_last_plan)
     double *d_tables = nullptr, *d_phhi = nullptr, *d_phlo = nullptr, *d_ftay = nullptr, *d_delay = nullptr;
     double* d_swg = nullptr;  // solar-wind geometry per evaluation row (k_sw_geom); null: no instance has NE_SW
     double *d_M = nullptr, *d_rt = nullptr, *d_rp = nullptr, *d_chi2 = nullptr, *d_chi2lin = nullptr;
@@ -8356,6 +8357,69 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         }
     }
     const int nparts = ctx->nsplit + ((mode == 1 && ctx->max_nep > 0) ? 1 : 0);
+    const int cmp = ctx->m_compact;
+    // solve plan: the DMX-eliminated solve (k_solve_dmx) for compact-layout instances when
+    // every such instance fits its LDS budget; the others (and everything in the full
+    // layout) go to the blocked MFMA solve, or the column-by-column one beyond its budget.
+    // Host arithmetic on the batch's widths only, done before the first launch so that a
+    // batch no solve kernel can take is refused with nothing enqueued.
+    int Ks = 0, Kn = 0, ndmx_inst = 0;
+    bool dmx_ok = cmp && ctx->blocked_solve;
+    size_t lds_x = 0;
+    for (int pi : ctx->upsr) {
+        const PsrHost& ph = ctx->psrs[pi];
+        const pint_spec_t& sp = ph.spec;
+        const int kn = mode == 1 ? 2 * sp.nred + 1 : 0;
+        Kn = std::max(Kn, kn);
+        if (cmp && ph.dev.dsplit) {
+            ndmx_inst++;
+            const int kd = mode == 0 ? ph.dev.red0c : ph.dev.Kd;
+            const int nbd = (kd + 15) / 16, nbk = (ph.dev.ndc + 15) / 16, nbs = (kn + 15) / 16;
+            const int blk = nbd * (nbd + 1) / 2 + nbd * nbk;
+            if (blk > SD_MAXBLK || nbd > 17 || nbs > BS_MAXNB) dmx_ok = false;
+            lds_x = std::max(lds_x, sizeof(double) * ((size_t)std::max(blk, nbs * (nbs + 1) / 2) * 256 +
+                                                      (size_t)(5 * nbd + 6 * nbk) * 16));
+            if (lds_x > 160 * 1024 - 512) dmx_ok = false;  // (the kernel's static LDS beside it)
+        } else {
+            Ks = std::max(Ks, mode == 0 ? sp.ncol : ph.K);
+        }
+    }
+    if (!dmx_ok) {  // every instance through the general solve
+        for (int pi : ctx->upsr) Ks = std::max(Ks, mode == 0 ? ctx->psrs[pi].spec.ncol : ctx->psrs[pi].K);
+        ndmx_inst = 0;
+    }
+    const int skip = ndmx_inst > 0 ? 1 : 0;
+    // Woodbury Sigma factor: in k_solve_dmx's grid when every instance is solved there, else
+    // on the side stream, concurrent with the per-instance solve
+    int do_sigma = 0, fuse_sigma = 0, side_sigma = 0, nbs_sig = 0;
+    size_t lds_s = 0;
+    if (mode == 1) {
+        int kn = 0;
+        bool any = false;
+        for (int pi : ctx->upsr) {
+            const PsrHost& ph = ctx->psrs[pi];
+            if (ph.spec.nred > 0 || ph.dev.nep > 0) { any = true; kn = std::max(kn, 2 * ph.spec.nred + 1); }
+        }
+        nbs_sig = (kn + 15) / 16;
+        lds_s = sizeof(double) * (size_t)nbs_sig * (nbs_sig + 1) / 2 * 256;
+        if (any && nbs_sig <= BS_MAXNB && ctx->blocked_solve && skip && Ks == 0) fuse_sigma = 1;
+        else if (any && nbs_sig <= BS_MAXNB && ctx->blocked_solve) side_sigma = 1;
+        else if (any) do_sigma = 1;  // the column-by-column solve factors it (beyond the blocked LDS budget)
+    }
+    const int nbx = std::max((Ks + 15) / 16, (Kn + 15) / 16);
+    const bool col_solve = !(skip && Ks == 0) && !(nbx <= BS_MAXNB && ctx->blocked_solve);
+    const size_t lds_col = sizeof(double) * ((size_t)ctx->maxK * (ctx->maxK + 1) / 2 + 5 * ctx->maxK + 8);
+    ctx->plan = pint_plan_t{};
+    if (col_solve && lds_col > 160 * 1024) { ctx->err = "normal matrix too large for LDS solve"; return PINT_E_INVALID; }
+    if (do_sigma && !col_solve) {  // Sigma too large for k_sigma but the main solve on the blocked kernels
+        ctx->err = "Woodbury Sigma too large for the LDS factorisation";
+        return PINT_E_INVALID;
+    }
+    pint_plan_t pl{};
+    pl.nsplit = ctx->nsplit;
+    pl.fuse_sigma = fuse_sigma;
+    pl.side_sigma = side_sigma;
+    pl.do_sigma = do_sigma;
     if (ctx->sigma_pending) {  // the previous k_sigma reads the Gram buffer this step overwrites
         HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));
         ctx->sigma_pending = false;
@@ -8371,7 +8435,6 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
                            ctx->d_dmxv, ctx->d_eC);
         HIPCHK(hipGetLastError());
     }
-    const int cmp = ctx->m_compact;
     const bool vgp = cmp && ctx->n_vg > 0;  // k_gram_v path for the vg instances
     // PhaseOffset with a frozen PHOFF and correlated noise: the Woodbury ones row (k_onesrow)
     const double* ones = nullptr;
@@ -8398,6 +8461,9 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         hipLaunchKernelGGL(k_dmx_rows, dim3(ctx->max_ndc, ctx->ninst), dim3(256), lds, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, ctx->d_M, ctx->d_rt, ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
         HIPCHK(hipGetLastError());
+        pl.dmx_rows = 1;
+        pl.dmx = any_gather ? 1 : 0;
+        pl.ecorr_dmx = (mode == 1 && ctx->max_nep > 0) ? 1 : 0;
         if (any_gather) {
             hipLaunchKernelGGL(k_dmx, dim3(ctx->max_ndc, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs,
                                ctx->d_inst, ctx->d_M, ctx->d_rt, ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
@@ -8433,6 +8499,8 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
                 hipLaunchKernelGGL(k_gram_s, dim3(ctx->nsplit, (kg.count + 3) / 4), dim3(256), 0, ctx->stream,
                                    ctx->d_psrs, di, kg.count, ctx->d_M, ctx->d_rt, ctx->nsplit, cmp, ctx->d_G,
                                    ctx->d_colsq);
+                pl.gram_s = 1;
+                if (mode == 1 && ctx->max_nep > 0) pl.gram_ecorr = 1, pl.gram_t_mask |= 1 << 1;
                 if (mode == 1 && ctx->max_nep > 0)
                     hipLaunchKernelGGL((k_gram<1, gram_ch(1), true>), dim3(1, kg.count), dim3(GTHREADS),
                                        sizeof(double) * ((size_t)kg.maxKp * (gram_ch(1) + 2) + gram_ch(1)),
@@ -8445,7 +8513,8 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
             for (int virt = 0; virt < 2; virt++) {
                 if (virt && !(mode == 1 && ctx->max_nep > 0)) break;
                 dim3 grid(virt ? 1 : ctx->nsplit, kg.count);
-#define PINT_GRAM_CASE(TT)                                                                                         \
+                if (T >= 1 && T <= GMAXT_ALL) pl.gram_t_mask |= 1 << T, pl.gram_ecorr |= virt;
+#define PINT_GRAM_CASE(TT)                                                                                        \
                 case TT:                                                                                           \
                     if (virt) hipLaunchKernelGGL((k_gram<TT, gram_ch(TT), true>), grid, dim3(GTHREADS), lds,      \
                                                  ctx->stream, ctx->d_psrs, di, ctx->d_M, ctx->d_rt, ctx->d_esum,  \
@@ -8508,6 +8577,10 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
                 default: ctx->err = "k_gram_v layout out of range"; return PINT_E_INVALID;
             }
 #undef PINT_GRAMV
+            if (pl.nvkey < PINT_PLAN_MAXVKEY) {
+                pl.vkey[pl.nvkey] = kg.T;
+                pl.vkey_vb[pl.nvkey++] = (ctx->vb_on && kg.T % 10 <= 6) ? 1 : 0;
+            }
         }
         if (ext_t) ctx->rec[12] = ctx->rec[13] = true;
         else if (gram_mark) record(ctx, 13);
@@ -8515,52 +8588,6 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         record(ctx, 13);
     }
     HIPCHK(hipGetLastError());
-    // solve plan: the DMX-eliminated solve (k_solve_dmx) for compact-layout instances when
-    // every such instance fits its LDS budget; the others (and everything in the full
-    // layout) go to the blocked MFMA solve, or the column-by-column one beyond its budget.
-    int Ks = 0, Kn = 0, ndmx_inst = 0;
-    bool dmx_ok = cmp && ctx->blocked_solve;
-    size_t lds_x = 0;
-    for (int pi : ctx->upsr) {
-        const PsrHost& ph = ctx->psrs[pi];
-        const pint_spec_t& sp = ph.spec;
-        const int kn = mode == 1 ? 2 * sp.nred + 1 : 0;
-        Kn = std::max(Kn, kn);
-        if (cmp && ph.dev.dsplit) {
-            ndmx_inst++;
-            const int kd = mode == 0 ? ph.dev.red0c : ph.dev.Kd;
-            const int nbd = (kd + 15) / 16, nbk = (ph.dev.ndc + 15) / 16, nbs = (kn + 15) / 16;
-            const int blk = nbd * (nbd + 1) / 2 + nbd * nbk;
-            if (blk > SD_MAXBLK || nbd > 17 || nbs > BS_MAXNB) dmx_ok = false;
-            lds_x = std::max(lds_x, sizeof(double) * ((size_t)std::max(blk, nbs * (nbs + 1) / 2) * 256 +
-                                                      (size_t)(5 * nbd + 6 * nbk) * 16));
-            if (lds_x > 160 * 1024 - 512) dmx_ok = false;  // (the kernel's static LDS beside it)
-        } else {
-            Ks = std::max(Ks, mode == 0 ? sp.ncol : ph.K);
-        }
-    }
-    if (!dmx_ok) {  // every instance through the general solve
-        for (int pi : ctx->upsr) Ks = std::max(Ks, mode == 0 ? ctx->psrs[pi].spec.ncol : ctx->psrs[pi].K);
-        ndmx_inst = 0;
-    }
-    const int skip = ndmx_inst > 0 ? 1 : 0;
-    // Woodbury Sigma factor: in k_solve_dmx's grid when every instance is solved there, else
-    // on the side stream, concurrent with the per-instance solve
-    int do_sigma = 0, fuse_sigma = 0, side_sigma = 0, nbs_sig = 0;
-    size_t lds_s = 0;
-    if (mode == 1) {
-        int kn = 0;
-        bool any = false;
-        for (int pi : ctx->upsr) {
-            const PsrHost& ph = ctx->psrs[pi];
-            if (ph.spec.nred > 0 || ph.dev.nep > 0) { any = true; kn = std::max(kn, 2 * ph.spec.nred + 1); }
-        }
-        nbs_sig = (kn + 15) / 16;
-        lds_s = sizeof(double) * (size_t)nbs_sig * (nbs_sig + 1) / 2 * 256;
-        if (any && nbs_sig <= BS_MAXNB && ctx->blocked_solve && skip && Ks == 0) fuse_sigma = 1;
-        else if (any && nbs_sig <= BS_MAXNB && ctx->blocked_solve) side_sigma = 1;
-        else if (any) do_sigma = 1;  // the column-by-column solve factors it (beyond the blocked LDS budget)
-    }
     GredArgs gra{ctx->nsplit, nparts, cmp, ctx->vb_on, ctx->d_G, ctx->d_colsq, ctx->d_Sdp, ctx->d_dmxv,
                  ctx->d_Sd, ctx->d_DD, ctx->d_DCS, ctx->d_BFp};
     if (nparts > 1 || vgp) {
@@ -8576,6 +8603,7 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         hipLaunchKernelGGL(k_greduce, dim3(nbg + (vgp ? (ctx->max_ndc + 3) / 4 : 0), ctx->ninst), dim3(256), 0, ctx->stream,
                            ctx->d_psrs, ctx->d_inst, nbg, gra);
         HIPCHK(hipGetLastError());
+        pl.greduce = 1;
         record(ctx, 15);
     }
     if (ctx->wbfit && cmp) {  // WidebandTOAFitter: the DM rows join the normal equations
@@ -8583,11 +8611,13 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         hipLaunchKernelGGL(k_wb_gram, dim3(ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
                            ctx->d_tables, ctx->d_ic, ctx->nsplit, ctx->d_G, ctx->d_colsq, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
         HIPCHK(hipGetLastError());
+        pl.wb_gram = 1;
     }
     record(ctx, 7);
     if (side_sigma) {
         HIPCHK(hipEventRecord(ctx->ev_gram, ctx->stream));
         HIPCHK(hipStreamWaitEvent(ctx->sstream, ctx->ev_gram, 0));
+        pl.sigma_waves = nbs_sig <= 5 ? 4 : 16;
         if (nbs_sig <= 5)
             hipLaunchKernelGGL(k_sigma<4>, dim3(ctx->ninst), dim3(256), lds_s, ctx->sstream, ctx->d_psrs, ctx->d_inst,
                                ctx->d_tables, ctx->d_G, cmp, ctx->d_Sd, ctx->d_DD, ctx->d_sigL, ctx->d_status, ones);
@@ -8680,14 +8710,16 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         if (w8) PINT_SOLVE_DMX(8); else PINT_SOLVE_DMX(16);
 #undef PINT_SOLVE_DMX
         HIPCHK(hipGetLastError());
+        pl.solve_dmx_waves = w8 ? 8 : 16;
+        pl.schur = pre;
+        pl.cov_deferred = xw != nullptr;
         ctx->cov_pending = xw != nullptr;
         ctx->cov_mode = mode;
         ctx->cov_lds = lds_x;
     }
-    const int nbx = std::max((Ks + 15) / 16, (Kn + 15) / 16);
     if (skip && Ks == 0) {
         // every instance went through k_solve_dmx
-    } else if (nbx <= BS_MAXNB && ctx->blocked_solve) {
+    } else if (!col_solve) {
         const int ldsw = nbx * (nbx + 1) / 2 * 256 + 2 * 16 * nbx;  // doubles per instance
         const int ldsw1 = ldsw + 3 * 16 * nbx;  // (+ the three scratch vectors: one-wave form)
         size_t lds_b = sizeof(double) * (size_t)ldsw;
@@ -8696,6 +8728,7 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
         if (nbx <= 1 && ctx->small && ctx->lane_solve && !skip && Ks <= 8) {
             // K <= 8 (a grid's points): a lane per instance
             const int KT = Ks <= 4 ? 4 : 8;
+            pl.solve = KT == 4 ? PINT_PLAN_SOLVE_LANES4 : PINT_PLAN_SOLVE_LANES8;
             if (KT == 4)
                 hipLaunchKernelGGL(k_solve_lanes<4>, dim3((ctx->ninst + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_psrs,
                                    ctx->d_inst, ctx->d_G, ctx->d_colsq, ctx->nsplit, mode, ctx->d_dpars, ctx->d_errs,
@@ -8722,21 +8755,18 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
                                ctx->d_DCS, ctx->d_dpars, ctx->d_errs,
                                ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, skip, ctx->d_rscr, ctx->refine,
                                ctx->ninst, ldsw);
-    } else {
-        int K = ctx->maxK;
-        size_t lds_s = sizeof(double) * ((size_t)K * (K + 1) / 2 + 5 * K + 8);
-        if (lds_s > 160 * 1024) { ctx->err = "normal matrix too large for LDS solve"; return PINT_E_INVALID; }
-        hipLaunchKernelGGL(k_solve, dim3(ctx->ninst), dim3(SOLVE_T), lds_s, ctx->stream, ctx->d_psrs, ctx->d_inst,
+        if (!pl.solve)
+            pl.solve = (nbx <= 2 && ctx->small) ? PINT_PLAN_SOLVE_BLK1
+                                                : (nbx <= 5 ? PINT_PLAN_SOLVE_BLK4 : PINT_PLAN_SOLVE_BLK16);
+    } else {  // (its LDS budget was checked before the first launch)
+        hipLaunchKernelGGL(k_solve, dim3(ctx->ninst), dim3(SOLVE_T), lds_col, ctx->stream, ctx->d_psrs, ctx->d_inst,
                            ctx->d_tables, ctx->d_G, ctx->d_colsq, ctx->nsplit, nparts, mode, cmp, ctx->d_Sd, ctx->d_DD,
                            ctx->d_DCS, ctx->d_work, ctx->d_dpars,
                            ctx->d_errs, ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, skip, do_sigma, ones);
-    }
-    if (do_sigma && !(nbx > BS_MAXNB || !ctx->blocked_solve)) {
-        // Sigma too large for k_sigma but the main solve went to the blocked kernels
-        ctx->err = "Woodbury Sigma too large for the LDS factorisation";
-        return PINT_E_INVALID;
+        pl.solve = PINT_PLAN_SOLVE_COLUMN;
     }
     HIPCHK(hipGetLastError());
+    ctx->plan = pl;
     record(ctx, 8);
     if (ctx->capturing) HIPCHK(hipEventRecord(ctx->ev_solved, ctx->stream));
     if (ctx->lazy) return PINT_OK;
@@ -9150,8 +9180,15 @@ int pint_query(pint_ctx* ctx, int key) {
     if (key == PINT_QUERY_NVGRAM) return ctx->n_vg;
     if (key == PINT_QUERY_NSPLIT) return ctx->nsplit;
     if (key == PINT_QUERY_NSPINEVAL) return ctx->n_spin_eval;
+    if (key == PINT_QUERY_WFUSE) return ctx->wfuse ? 1 : 0;
     ctx->err = "unknown query";
     return -PINT_E_INVALID;
+}
+
+int pint_last_plan(pint_ctx* ctx, pint_plan_t* out) {
+    if (!ctx || !out) return PINT_E_INVALID;
+    *out = ctx->plan;
+    return PINT_OK;
 }
 
 int pint_check(pint_ctx* ctx) {

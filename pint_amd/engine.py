@@ -1077,6 +1077,28 @@ class Session:
         """The Gram's N-split count of the current batch (row blocks per instance)."""
         return int(self.L.pint_query(self.ctx, 2))
 
+    def wfuse(self):
+        """Whether the batch's residual pass forms the post-fit Woodbury dots (every noise basis a
+        PLRedNoise series of at most 63 modes)."""
+        return bool(self.L.pint_query(self.ctx, 4))
+
+    def last_plan(self):
+        """The launch plan of the last fit_step (pint_last_plan) as a dict: the k_gram tile
+        counts T launched (gram_T), the k_gram_v (key, vb) launches (gram_v), the general solve
+        kernel's name (solve) and the other fields of pint_plan_t as they are.  All zero / empty
+        after a fit_step that refused its batch before launching."""
+        p = L.PlanT()
+        self._check(self.L.pint_last_plan(self.ctx, C.byref(p)))
+        out = {"gram_T": tuple(T for T in range(1, 10) if (p.gram_t_mask >> T) & 1),
+               "gram_v": tuple((int(p.vkey[i]), bool(p.vkey_vb[i])) for i in range(p.nvkey)),
+               "solve": L.PLAN_SOLVE[p.solve]}
+        for name in ("gram_ecorr", "gram_s", "greduce", "dmx_rows", "dmx", "ecorr_dmx", "wb_gram", "fuse_sigma",
+                     "side_sigma", "do_sigma", "schur", "cov_deferred"):
+            out[name] = bool(getattr(p, name))
+        for name in ("nsplit", "solve_dmx_waves", "sigma_waves"):
+            out[name] = int(getattr(p, name))
+        return out
+
     def check(self):
         try:
             self._check(self.L.pint_check(self.ctx))

@@ -39,9 +39,11 @@ def _spawn(target, world=2):
 
 
 # ---- grid_chisq -------------------------------------------------------------------------
-def _stub_grid(gu):
+def _stub_grid(gu, patch=setattr):
     """Replace the device parts of grid_chisq: the upload (host layout only) and the batch
-    fit (chi2 a fixed function of each point's table; the 'fitted' table shifts DM)."""
+    fit (chi2 a fixed function of each point's table; the 'fitted' table shifts DM).  A test
+    passes monkeypatch.setattr as `patch`: the stubs must not outlive it in the pytest process
+    (left in place they answered every later grid test of a whole-suite run on a GPU)."""
     from pint_amd.engine import build_layout
 
     def session(model, parnames, toas, gls, npipe=1):
@@ -61,8 +63,8 @@ def _stub_grid(gu):
         ft[:, lay.offsets["DM"]] += np.arange(len(tabs)) * 0.0  # unchanged DM
         return chi2, ft
 
-    gu._grid_session = session
-    gu._fit_block = fit_block
+    patch(gu, "_grid_session", session)
+    patch(gu, "_fit_block", fit_block)
 
 
 def _grid_args():
@@ -91,10 +93,10 @@ def _grid_worker(rank, world, port, q):
         dist.destroy_process_group()
 
 
-def test_grid_chisq_two_ranks_gloo():
+def test_grid_chisq_two_ranks_gloo(monkeypatch):
     out = _spawn(_grid_worker)
     import pint_amd.gridutils as gu
-    _stub_grid(gu)
+    _stub_grid(gu, monkeypatch.setattr)
     f, vals = _grid_args()
     want, wex = gu.grid_chisq(f, ("F0", "F1"), vals, extraparnames=["DM"])  # one process
     wbest = gu.best_point(want, ("F0", "F1"), vals)
@@ -136,13 +138,13 @@ def _tuple_worker(rank, world, port, q):
         dist.destroy_process_group()
 
 
-def test_tuple_chisq_two_ranks_gloo():
+def test_tuple_chisq_two_ranks_gloo(monkeypatch):
     """tuple_chisq / tuple_chisq_derived / grid_chisq_derived (gridutils.py:588/:773/:392)
     split into contiguous per-rank blocks and all-gathered: every rank returns exactly the
     one-process result, in list order."""
     out = _spawn(_tuple_worker)
     import pint_amd.gridutils as gu
-    _stub_grid(gu)
+    _stub_grid(gu, monkeypatch.setattr)
     f, pts, dpts = _tuple_args()
     want, wex = gu.tuple_chisq(f, ("F0", "F1"), pts, extraparnames=["DM"])
     assert want.shape == (7,) and wex["DM"].shape == (7,)

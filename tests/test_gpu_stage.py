@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from golden_util import GOLDEN, chi2_bar, load, ref_value, rms_ps
+from ld_util import ld_inverse, ld_solve
 
 pytestmark = pytest.mark.gpu
 
@@ -169,42 +170,6 @@ def test_stage_gram_step(name):
     assert c_dev <= max(1e-9, 3 * c_ref, c_in), (c_dev, c_ref, c_in)
     assert de.max() <= 1e-3 and dc.max() <= 5e-3
     bf.close()
-
-
-def ld_inverse(A):
-    """Gauss-Jordan inverse with partial pivoting in longdouble."""
-    A = np.array(A, dtype=np.longdouble)
-    n = len(A)
-    M = np.concatenate([A, np.eye(n, dtype=np.longdouble)], axis=1)
-    for k in range(n):
-        p = k + int(np.argmax(np.abs(M[k:, k])))
-        if p != k:
-            M[[k, p]] = M[[p, k]]
-        M[k] /= M[k, k]
-        f = M[:, k].copy()
-        f[k] = 0
-        M -= np.outer(f, M[k])
-    return M[:, n:]
-
-
-def ld_solve(A, b):
-    """Gaussian elimination with partial pivoting in longdouble (numpy's solvers drop to
-    float64): the reference solution of a stage's linear system."""
-    A = np.array(A, dtype=np.longdouble)
-    b = np.array(b, dtype=np.longdouble)
-    n = len(b)
-    for k in range(n):
-        p = k + int(np.argmax(np.abs(A[k:, k])))
-        if p != k:
-            A[[k, p]] = A[[p, k]]
-            b[[k, p]] = b[[p, k]]
-        f = A[k + 1:, k] / A[k, k]
-        A[k + 1:, k:] -= np.outer(f, A[k, k:])
-        b[k + 1:] -= f * b[k]
-    x = np.zeros(n, dtype=np.longdouble)
-    for k in range(n - 1, -1, -1):
-        x[k] = (b[k] - A[k, k + 1:] @ x[k + 1:]) / A[k, k]
-    return x
 
 
 @pytest.mark.parametrize("name", GLS)
