@@ -152,8 +152,14 @@ enum {
     PINT_B_EPS1DOT, PINT_B_EPS2DOT, PINT_B_H3, PINT_B_H4, PINT_B_STIGMA, PINT_B_KIN, PINT_B_KOM,
     PINT_B_NPAR0,                        /* the length of spec.o_bin                                   */
     PINT_B_SHAPMAX = PINT_B_NPAR0, PINT_B_LNEDOT,   /* their slots: PINT_SPEC_O_BINX(spec, id)          */
-    PINT_B_NPAR
+    PINT_B_NPAR,
+    PINT_B_FB0 = PINT_B_NPAR             /* FBn: PINT_B_FB0 + n, n < PINT_MAX_FB; its slot: PINT_SPEC_O_FB(spec)
+                                            + 2 n.  A PINT_COL_BIN column like the others: d orbits / d FBn =
+                                            tt0^(n+1) / (n+1)! (times 2 pi into Phi / M) and d pbprime / d FBn =
+                                            -pbprime^2 tt0^n / n!, carried through the chains of the PB column
+                                            (binary_orbits.py:205-231), per 1 / s^(n+1), the par unit            */
 };
+#define PINT_MAX_FB 20                   /* orbital-frequency terms FB0 .. FB19 per pulsar                  */
 /* binary models (spec.binary).
  * dds (DDS_model.py): DD with SINI = 1 - exp(-SHAPMAX) wherever DD uses SINI; d SINI / d SHAPMAX =
  *   exp(-SHAPMAX), no other parameter moves SINI.  SHAPMAX (dimensionless) must be > -log 2.
@@ -171,10 +177,21 @@ enum {
  *   the Shapiro delay are ELL1's.  d eps2 / d EPS2 = +d eps1 / d EPS1 (the reference has the
  *   opposite sign; this is the correct one).
  * A dds / ddh row whose Shapiro argument logNum is <= 0 sets PINT_E_KEPLER like a failed Kepler
- * solve. */
+ * solve.
+ * The orbital-frequency orbit (binary_orbits.py:158-239 OrbitFBX; ELL1, ELL1H, DD and BT): when
+ * PINT_SPEC_NFB(spec) > 0 the orbit is orbits = sum_n FBn tt0^(n+1) / (n+1)! (double-double), the
+ * period pbprime = 1 / sum_n FBn tt0^n / n! and its rate pbdot = -pbprime^2 sum_{n>=1} FBn tt0^(n-1) /
+ * (n-1)! wherever the model uses pb() and pbdot(); PB is absent (o_bin[PINT_B_PB] = -1), PBDOT and
+ * XPBDOT are ignored and their columns are zero.  T0 (DD, BT): d orbits / d T0 = -1 / pbprime per
+ * second, d pbprime / d T0 = -pbdot (the reference's column is zero; this is the correct one).  A row
+ * whose orbital frequency is not positive sets PINT_E_KEPLER.  Such a pulsar's rows are evaluated by
+ * a kernel build of their own (block kinds PINT_BLK_FB_*), never by the builds of the period form. */
 enum { PINT_BIN_NONE = 0, PINT_BIN_ELL1 = 1, PINT_BIN_DD = 2, PINT_BIN_ELL1H = 3, PINT_BIN_BT = 4, PINT_BIN_DDK = 5,
        PINT_BIN_DDS = 6, PINT_BIN_DDH = 7, PINT_BIN_ELL1K = 8,
-       PINT_NBIN = 9 };
+       PINT_NBIN = 9,
+       /* block kinds of the evaluation past the binary models: the FBn form of ELL1, DD, ELL1H, BT */
+       PINT_BLK_FB_ELL1 = 9, PINT_BLK_FB_DD = 10, PINT_BLK_FB_ELL1H = 11, PINT_BLK_FB_BT = 12,
+       PINT_NBLK = 13 };
 
 typedef struct {
     int32_t nf;             /* spin terms F0..F{nf-1}                                   */
@@ -236,7 +253,12 @@ typedef struct {
                                the ids past o_bin (PINT_B_SHAPMAX, PINT_B_LNEDOT), 0 = absent: read
                                with PINT_SPEC_O_BINX.  Kept in the reserve, biased by one, so that
                                every field keeps its offset and a model without them keeps its spec
-                               bytes (all-zero reserve).  rsv_[2]: unused reserve (keeps the header a whole number of 16-byte words)  */
+                               bytes (all-zero reserve).  rsv_[2]: the FBn block, nfb << 24 | (1 + the
+                               table slot of FB0), 0 = the period form: nfb dd pairs FB0 .. FB{nfb-1},
+                               contiguous and ascending; read with PINT_SPEC_NFB / PINT_SPEC_O_FB.
+                               pint_add_pulsar returns -PINT_E_INVALID for nfb outside 1..PINT_MAX_FB, a
+                               block outside the table, a binary model other than ELL1, ELL1H, DD, BT,
+                               or a PB slot beside it                                               */
     int32_t col_kind[PINT_MAX_COLS];
     int32_t col_index[PINT_MAX_COLS];
     int32_t col_toff[PINT_MAX_COLS];  /* table offset of the column's parameter (-1: Offset) */
@@ -244,6 +266,10 @@ typedef struct {
 
 /* table slot of binary parameter id >= PINT_B_NPAR0 (-1 absent) */
 #define PINT_SPEC_O_BINX(spec, id) ((spec).rsv_[(id) - PINT_B_NPAR0] - 1)
+/* the FBn block: the number of terms (0: the period form) and the table slot of FB0 (-1 absent) */
+#define PINT_SPEC_NFB(spec) ((int)((uint32_t)(spec).rsv_[2] >> 24))
+#define PINT_SPEC_O_FB(spec) ((int)((uint32_t)(spec).rsv_[2] & 0xffffffu) - 1)
+#define PINT_SPEC_FB(o_fb, nfb) ((int32_t)(((uint32_t)(nfb) << 24) | (uint32_t)((o_fb) + 1)))
 
 /* ---- context -------------------------------------------------------------------- */
 typedef struct pint_ctx pint_ctx;

@@ -17,6 +17,8 @@ MAX_COLS = 320
 EIG_MAXDEG = 8  # PINT_EIG_MAXDEG
 NSLOT = 4  # pipeline slots (pint_step_end / pint_check_step): set from the library's pint_nslot() by lib()
 B_NPAR = 27   # PINT_B_NPAR0: the length of o_bin; the ids past it (SHAPMAX, LNEDOT): 1 + slot in rsv_
+B_FB0 = 29    # PINT_B_FB0: the column id of FBn is B_FB0 + n; the block: rsv_[2] = nfb << 24 | (1 + FB0's slot)
+MAX_FB = 20   # PINT_MAX_FB
 BIN_NONE, BIN_ELL1, BIN_DD, BIN_ELL1H, BIN_BT, BIN_DDK, BIN_DDS, BIN_DDH, BIN_ELL1K = range(9)
 
 COL_OFFSET, COL_F, COL_LON, COL_LAT, COL_PMLON, COL_PMLAT, COL_PX, COL_DM, COL_DMX, COL_FD, COL_JUMP, COL_BIN, COL_ZERO, COL_NESW, COL_GLITCH, COL_WX, COL_DMWX, COL_CM, COL_CMWX, COL_FDJUMP, COL_FDJUMPDM = range(21)

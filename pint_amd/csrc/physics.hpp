@@ -488,6 +488,55 @@ PD void orbit_phase(dd tt0, dd ipbs, double pbdot_sum, BinState& B) {
     B.Phi = B.orbits_frac * TWO_PI;  // orbit_phase(): (orbits - floor)*2pi (binary_orbits.py:25)
 }
 
+// OrbitFBX (binary_orbits.py:158-239): the orbit from the orbital frequency and its derivatives,
+// the block of PINT_SPEC_NFB(S) dd pairs at PINT_SPEC_O_FB(S).  orbits = taylor_horner(tt0, [0, FB0,
+// FB1, ...]) (:183) by spin_phase's dd Horner form, so that FB0 tt0 (thousands of orbits) and the
+// higher terms keep the fraction to dd precision; pbprime = 1 / taylor_horner_deriv(.., 1) (:188)
+// and pbdot = -pbprime^2 taylor_horner_deriv(.., 2) (:193) in double, as the reference's period
+// form has them.  Sets what the period form's lines set: B.pb / B.ipb (pbprime and its inverse),
+// B.PBDOT = pbdot() (so that d_Phi_d_TASC and d_pbprime_d_T0 = -pbdot read it), B.XPBDOT = 0 (no
+// part in this orbit), B.PBs / B.iPBs = 1 / FB0, FB0.  A frequency that is not positive (or NaN)
+// is replaced by 1, so that nothing downstream divides by 0, and PINT_E_KEPLER is returned (0 otherwise).
+PD int orbit_fbx(const pint_spec_t& S, const double* P, dd tt, BinState& B) {
+    const int m = PINT_SPEC_NFB(S), o = PINT_SPEC_O_FB(S);
+    const double t = B.tt0;
+    dd r = pdd(P, o + 2 * (m - 1));
+    double f = dd_to_d(r), fd = f;
+    for (int j = m - 1; j >= 1; j--) {
+        const dd c = pdd(P, o + 2 * (j - 1));
+        r = dd_add(dd_div_int(dd_mul(r, tt), j + 1), c);
+        f = f * t * inv_int(j) + dd_to_d(c);
+        if (j >= 2) fd = fd * t * inv_int(j - 1) + dd_to_d(c);
+    }
+    if (m < 2) fd = 0.0;
+    const dd orb = dd_mul(r, tt);
+    const dd fl = dd_floor(orb);
+    B.floor_orbits = dd_to_d(fl);
+    B.orbits_frac = dd_to_d(dd_sub(orb, fl));
+    B.Phi = B.orbits_frac * TWO_PI;
+    int status = 0;
+    if (!(f > 0.0)) {
+        status = PINT_E_KEPLER;
+        f = 1.0;
+    }
+    B.ipb = f;
+    B.pb = 1.0 / f;
+    B.PBDOT = -B.pb * B.pb * fd;
+    B.XPBDOT = 0.0;
+    B.iPBs = pval(P, o);
+    B.PBs = 1.0 / B.iPBs;
+    return status;
+}
+
+// the seeds of an FBn column (n = pid - PINT_B_FB0): d_orbits_d_FBX = tt0^(n+1) / (n+1)! times 2 pi
+// (:205-217) and d_pbprime_d_FBX = -pbprime^2 tt0^n / n! (:219-231)
+PD void fbx_seeds(const BinState& B, int n, double& d_M, double& d_pb) {
+    double p = 1.0;
+    for (int k = 1; k <= n; k++) p *= B.tt0 * inv_int(k);
+    d_pb = -B.pb * B.pb * p;
+    d_M = TWO_PI * (p * B.tt0 * inv_int(n + 1));
+}
+
 // ---- ELL1H Shapiro delay (ELL1H_model.py, Freire & Wex 2010) ------------------------
 // binary_ell1.py:383-405 picks the form: S.ell1h 1 = H3 alone (Eq. 19, stigma = 0), 2 = H3 + H4
 // (Eq. 19, stigma = H4/H3, harmonics 3..NHARMS), 3 = H3 + STIGMA (the exact Eq. 29).  Eq. 19:
@@ -551,20 +600,26 @@ PD double ell1h_shapiro(const pint_spec_t& S, const double* P, BinState& B) {
 // (:120-134); Drep, Drepp and the Shapiro delay stay ELL1's.  B.EPS1DOT / B.EPS2DOT then hold
 // d_eps1_d_EPS1 = (1 + LNEDOT dt) cos(OMDOT dt) and d_eps1_d_EPS2 = (1 + LNEDOT dt) sin(OMDOT dt),
 // B.EDOT LNEDOT (1/s), B.OMDOT_rs OMDOT (rad/s): the seeds of ell1k_deriv.
-template <bool H, bool KV = false>
+// FB: the orbit from FB0 ... FBn (orbit_fbx) in place of PB, PBDOT and XPBDOT.
+template <bool H, bool KV = false, bool FB = false>
 PD void ell1_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd tdb, double acc_delay, BinState& B) {
     dd tasc = pdd(P, S.o_bin[PINT_B_TASC]);
     // ttasc = (t - TASC) in s with t = tdbld*day - acc_delay (pulsar_binary.py:398, ELL1_model.py:42)
     dd tt = dd_add_d(dd_mul_d(dd_sub(tdb, tasc), DAYSEC), -acc_delay);
     B.tt0 = dd_to_d(tt);
-    dd PB = pdd(P, S.o_bin[PINT_B_PB]);
-    dd PBs = dd_mul_d(PB, DAYSEC);
-    B.PBs = dd_to_d(PBs);
-    B.PBDOT = binp(S, P, PINT_B_PBDOT);
-    B.XPBDOT = binp(S, P, PINT_B_XPBDOT);
-    orbit_phase(tt, dd_make(C.ipb_hi, C.ipb_lo), B.PBDOT + B.XPBDOT, B);
-    B.iPBs = C.ipb_hi + C.ipb_lo;
-    B.pb = B.PBs + B.PBDOT * B.tt0;  // pbprime (binary_orbits.py:107)
+    int fbst = 0;
+    if (FB) {
+        fbst = orbit_fbx(S, P, tt, B);
+    } else {
+        dd PB = pdd(P, S.o_bin[PINT_B_PB]);
+        dd PBs = dd_mul_d(PB, DAYSEC);
+        B.PBs = dd_to_d(PBs);
+        B.PBDOT = binp(S, P, PINT_B_PBDOT);
+        B.XPBDOT = binp(S, P, PINT_B_XPBDOT);
+        orbit_phase(tt, dd_make(C.ipb_hi, C.ipb_lo), B.PBDOT + B.XPBDOT, B);
+        B.iPBs = C.ipb_hi + C.ipb_lo;
+        B.pb = B.PBs + B.PBDOT * B.tt0;  // pbprime (binary_orbits.py:107)
+    }
     B.A1DOT = binp(S, P, PINT_B_A1DOT);
     B.a1 = binp(S, P, PINT_B_A1) + B.tt0 * B.A1DOT;
     if (KV) {
@@ -615,7 +670,7 @@ PD void ell1_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd
     B.Dre = B.a1 * B.R0;  // delayR (:317)
     B.Drep = B.a1 * B.R1;  // Drep (:398)
     B.Drepp = B.a1 * B.R2;  // Drepp (:478)
-    B.ipb = 1.0 / B.pb;
+    if (!FB) B.ipb = 1.0 / B.pb;
     B.nhat = TWO_PI * B.ipb;
     double nD = B.nhat * B.Drep;
     double delayI = B.Dre * (1 - nD + nD * nD + 0.5 * B.nhat * B.nhat * B.Dre * B.Drepp);  // :141-166
@@ -629,7 +684,7 @@ PD void ell1_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd
         B.hS_H3 = B.hS_sig = B.hS_Phi = B.dsig_dH3 = B.dsig_dH4 = 0.0;
     }
     B.delay = delayI + delayS;
-    B.status = 0;
+    B.status = FB ? fbst : 0;
 }
 
 // d(ELL1 delay)/d(par) per SI unit (ELL1_model.py:637 d_ELL1delay_d_par -> :174, :325, :406,
@@ -721,6 +776,19 @@ PD double ell1_deriv(const BinState& B, const Ell1Grad& g, int pid) {
     }
 }
 
+// The FBn orbit's columns: FBn through Phi and pb (ELL1_model.py:119-139, :171); PB, PBDOT and XPBDOT
+// move nothing (OrbitFBX has no derivative for them); TASC and the others are ell1_deriv's, where
+// B.PBDOT and B.ipb hold pbdot() and 1 / pb() of this orbit (d_Phi_d_TASC, :112-117).
+PD double ell1_deriv_fb(const BinState& B, const Ell1Grad& g, int pid) {
+    if (pid >= PINT_B_FB0) {
+        double d_M, d_pb;
+        fbx_seeds(B, pid - PINT_B_FB0, d_M, d_pb);
+        return g.Phi * d_M + g.pb * d_pb;
+    }
+    if (pid <= PINT_B_XPBDOT) return 0.0;
+    return ell1_deriv(B, g, pid);
+}
+
 // ELL1k's columns: ell1_deriv's dot products with the seeds of ELL1k_model.py:60-118 for EPS1, EPS2,
 // OMDOT, LNEDOT and TASC.  d_eps2_d_EPS2 = +d_eps1_d_EPS1: the reference returns the negative
 // (:102-103), which disagrees with its own numerical derivative and keeps its fitters from
@@ -810,21 +878,27 @@ PD void ddk_kopeikin(const pint_spec_t& S, const double* P, const double obs[3],
 // DDH (DDH_model.py, Freire & Wex 2010): SINI = 2 s / (1 + s^2), TM2 = H3 / s^3 (s = STIGMA); B.kSI =
 // {d SINI / d s, d TM2 / d s, d TM2 / d H3}.  In both a row with logNum <= 0 (reachable: SINI is
 // not bounded by the par file here) sets PINT_E_KEPLER instead of a NaN delay.
+// FB: the orbit from FB0 ... FBn (orbit_fbx) in place of PB, PBDOT and XPBDOT.
 enum { DDV_DD = 0, DDV_DDK = 1, DDV_DDS = 2, DDV_DDH = 3 };
-template <int V = DDV_DD>
+template <int V = DDV_DD, bool FB = false>
 PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd tdb, double acc_delay, BinState& B,
                   const double* kobs = nullptr, const double* kpsr = nullptr) {
     dd T0 = pdd(P, S.o_bin[PINT_B_T0]);
     dd tt = dd_add_d(dd_mul_d(dd_sub(tdb, T0), DAYSEC), -acc_delay);  // get_tt0 (binary_generic.py:372)
     B.tt0 = dd_to_d(tt);
-    dd PB = pdd(P, S.o_bin[PINT_B_PB]);
-    dd PBs = dd_mul_d(PB, DAYSEC);
-    B.PBs = dd_to_d(PBs);
-    B.PBDOT = binp(S, P, PINT_B_PBDOT);
-    B.XPBDOT = binp(S, P, PINT_B_XPBDOT);
-    orbit_phase(tt, dd_make(C.ipb_hi, C.ipb_lo), B.PBDOT + B.XPBDOT, B);
-    B.iPBs = C.ipb_hi + C.ipb_lo;
-    B.pb = B.PBs + B.PBDOT * B.tt0;
+    int fbst = 0;
+    if (FB) {
+        fbst = orbit_fbx(S, P, tt, B);
+    } else {
+        dd PB = pdd(P, S.o_bin[PINT_B_PB]);
+        dd PBs = dd_mul_d(PB, DAYSEC);
+        B.PBs = dd_to_d(PBs);
+        B.PBDOT = binp(S, P, PINT_B_PBDOT);
+        B.XPBDOT = binp(S, P, PINT_B_XPBDOT);
+        orbit_phase(tt, dd_make(C.ipb_hi, C.ipb_lo), B.PBDOT + B.XPBDOT, B);
+        B.iPBs = C.ipb_hi + C.ipb_lo;
+        B.pb = B.PBs + B.PBDOT * B.tt0;
+    }
     B.A1DOT = binp(S, P, PINT_B_A1DOT);
     B.a1 = binp(S, P, PINT_B_A1) + B.tt0 * B.A1DOT;
     B.EDOT = binp(S, P, PINT_B_EDOT);
@@ -851,7 +925,7 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     B.DTH = binp(S, P, PINT_B_DTH);
     B.A0 = binp(S, P, PINT_B_A0);
     B.B0 = binp(S, P, PINT_B_B0);
-    B.status = 0;
+    B.status = FB ? fbst : 0;
     double e = B.ecc, M = B.Phi;
     if (!(e >= 0.0 && e < 1.0)) { B.status = PINT_E_KEPLER; B.delay = 0; return; }
     // compute_eccentric_anomaly (binary_generic.py:337-370): Newton from E0 = M, tol 5e-15
@@ -874,7 +948,7 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     if (nu < 0) nu += TWO_PI;
     B.nu = TWO_PI * B.floor_orbits + nu;
     B.OMDOT_rs = binp(S, P, PINT_B_OMDOT) * (DEG_RAD / YR_S);
-    B.ipb = 1.0 / B.pb;
+    if (!FB) B.ipb = 1.0 / B.pb;
     B.k = B.OMDOT_rs * B.pb * INV_TWO_PI;             // DD_model.py:76 k
     B.omega = binp(S, P, PINT_B_OM) * DEG_RAD + B.nu * B.k;  // :86
     if (V == DDV_DDK) ddk_kopeikin(S, P, kobs, kpsr, B);
@@ -917,7 +991,11 @@ PD void ddm_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd 
     B.delay = delayI + delayS + delayA;
 }
 
-template <int V = DDV_DD>
+// FB (the FBn orbit): an FBn column is an orbit parameter's, with fbx_seeds' d_M and d_pb; PB, PBDOT
+// and XPBDOT move nothing; T0 has d_M = -2 pi / pbprime (d orbits / d T0 = -sum FBn tt0^n / n!) and
+// d_pb = -pbdot: the derivative itself, where the reference's OrbitFBX gives a zero column (it has no
+// d_orbits_d_T0, and T0 is not among its orbit_params).
+template <int V = DDV_DD, bool FB = false>
 PD double ddm_deriv(const BinState& B, int pid) {
     const double e = B.ecc, sE = B.sinE, cE = B.cosE, tt0 = B.tt0;
     const double iP = B.iPBs, iP2 = iP * iP;
@@ -925,9 +1003,16 @@ PD double ddm_deriv(const BinState& B, int pid) {
     // ---- seeds (binary_generic.py / binary_orbits.py / DD_model.py) ----
     bool orbit_par = (pid == PINT_B_PB || pid == PINT_B_PBDOT || pid == PINT_B_XPBDOT || pid == PINT_B_T0);
     double d_ecc = 0, d_a1 = 0, d_M = 0, d_pb = 0;
+    if (FB) {
+        if (pid <= PINT_B_XPBDOT) return 0.0;
+        if (pid >= PINT_B_FB0) {
+            orbit_par = true;
+            fbx_seeds(B, pid - PINT_B_FB0, d_M, d_pb);
+        }
+    }
     switch (pid) {
         case PINT_B_T0: d_ecc = -B.EDOT; d_a1 = -B.A1DOT;
-            d_M = ((B.PBDOT - B.XPBDOT) * tt0 * iP - 1.0) * TWO_PI * iP;  // binary_orbits.py:114
+            d_M = FB ? -TWO_PI * B.ipb : ((B.PBDOT - B.XPBDOT) * tt0 * iP - 1.0) * TWO_PI * iP;  // binary_orbits.py:114
             d_pb = -B.PBDOT; break;
         case PINT_B_ECC: d_ecc = 1; break;
         case PINT_B_EDOT: d_ecc = tt0; break;
@@ -1046,23 +1131,30 @@ PD double ddm_deriv(const BinState& B, int pid) {
 // (a1 cos(w) sqrt(1 - e^2) + GAMMA) sinE, delayR = 1 - 2 pi (a1 cos(w) sqrt(1-e^2) cosE -
 // a1 sin(w) sinE) / ((1 - e cosE) pb'), w = OM + OMDOT tt0 (binary_generic.py:631).
 // Kepler's equation as in DD.  B.Dre = L1 + L2, B.R0 = delayR.
+// FB: the orbit from FB0 ... FBn (orbit_fbx) in place of PB, PBDOT and XPBDOT.
+template <bool FB = false>
 PD void bt_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd tdb, double acc_delay, BinState& B) {
     dd T0 = pdd(P, S.o_bin[PINT_B_T0]);
     dd tt = dd_add_d(dd_mul_d(dd_sub(tdb, T0), DAYSEC), -acc_delay);  // get_tt0 (binary_generic.py:372)
     B.tt0 = dd_to_d(tt);
-    dd PBs = dd_mul_d(pdd(P, S.o_bin[PINT_B_PB]), DAYSEC);
-    B.PBs = dd_to_d(PBs);
-    B.PBDOT = binp(S, P, PINT_B_PBDOT);
-    B.XPBDOT = binp(S, P, PINT_B_XPBDOT);
-    orbit_phase(tt, dd_make(C.ipb_hi, C.ipb_lo), B.PBDOT + B.XPBDOT, B);
-    B.iPBs = C.ipb_hi + C.ipb_lo;
-    B.pb = B.PBs + B.PBDOT * B.tt0;
+    int fbst = 0;
+    if (FB) {
+        fbst = orbit_fbx(S, P, tt, B);
+    } else {
+        dd PBs = dd_mul_d(pdd(P, S.o_bin[PINT_B_PB]), DAYSEC);
+        B.PBs = dd_to_d(PBs);
+        B.PBDOT = binp(S, P, PINT_B_PBDOT);
+        B.XPBDOT = binp(S, P, PINT_B_XPBDOT);
+        orbit_phase(tt, dd_make(C.ipb_hi, C.ipb_lo), B.PBDOT + B.XPBDOT, B);
+        B.iPBs = C.ipb_hi + C.ipb_lo;
+        B.pb = B.PBs + B.PBDOT * B.tt0;
+    }
     B.A1DOT = binp(S, P, PINT_B_A1DOT);
     B.a1 = binp(S, P, PINT_B_A1) + B.tt0 * B.A1DOT;
     B.EDOT = binp(S, P, PINT_B_EDOT);
     B.ecc = binp(S, P, PINT_B_ECC) + B.tt0 * B.EDOT;
     B.GAMMA = binp(S, P, PINT_B_GAMMA);
-    B.status = 0;
+    B.status = FB ? fbst : 0;
     const double e = B.ecc, M = B.Phi;
     if (!(e >= 0.0 && e < 1.0)) { B.status = PINT_E_KEPLER; B.delay = 0; return; }
     double U = M, sU, cU;
@@ -1083,7 +1175,7 @@ PD void bt_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd t
     B.omega = binp(S, P, PINT_B_OM) * DEG_RAD + B.OMDOT_rs * B.tt0;
     sincos(B.omega, &B.sw, &B.cw);
     B.sqE = sqrt(1 - e * e);
-    B.ipb = 1.0 / B.pb;
+    if (!FB) B.ipb = 1.0 / B.pb;
     B.iomeE = 1.0 / (1 - e * cU);
     const double L1 = B.a1 * B.sw * (cU - e);
     const double L2 = (B.a1 * B.cw * B.sqE + B.GAMMA) * sU;
@@ -1096,6 +1188,9 @@ PD void bt_setup(const pint_spec_t& S, const double* P, const InstConst& C, dd t
 // d_BTdelay_d_par = delayR (d_delayL1_d_par + d_delayL2_d_par) (BT_model.py:258): delayR's own
 // derivatives are ignored, d_delayL1_d_ECC carries +a1 sin(w) (:189, as the reference has
 // it), d_delayL*_d_T0 goes through E only (:212-216); other orbit parameters through E.
+// FB (the FBn orbit): FBn through E with fbx_seeds' d_M; PB, PBDOT, XPBDOT nothing; T0 with d_M = -2 pi
+// / pbprime, the derivative itself (the reference's is zero, see ddm_deriv).
+template <bool FB = false>
 PD double bt_deriv(const BinState& B, int pid) {
     const double e = B.ecc, sE = B.sinE, cE = B.cosE, tt0 = B.tt0, a1 = B.a1;
     const double sw = B.sw, cw = B.cw, sq = B.sqE, iom = B.iomeE;
@@ -1104,6 +1199,14 @@ PD double bt_deriv(const BinState& B, int pid) {
     const double dL2_dE = (a1 * cw * sq + B.GAMMA) * cE;
     const double dE_dECC = sE * iom;
     double dL1 = 0.0, dL2 = 0.0, dE = 0.0;
+    if (FB) {
+        if (pid <= PINT_B_XPBDOT) return 0.0;
+        if (pid >= PINT_B_FB0) {
+            double d_M, d_pb;
+            fbx_seeds(B, pid - PINT_B_FB0, d_M, d_pb);
+            dE = d_M * iom;
+        }
+    }
     switch (pid) {
         case PINT_B_A1: case PINT_B_A1DOT: {
             const double f = (pid == PINT_B_A1DOT) ? tt0 : 1.0;
@@ -1122,7 +1225,7 @@ PD double bt_deriv(const BinState& B, int pid) {
         } break;
         case PINT_B_GAMMA: dL2 = sE; break;
         case PINT_B_T0:
-            dE = (((B.PBDOT - B.XPBDOT) * tt0 * iP - 1.0) * TWO_PI * iP - B.EDOT * sE) * iom;
+            dE = ((FB ? -TWO_PI * B.ipb : ((B.PBDOT - B.XPBDOT) * tt0 * iP - 1.0) * TWO_PI * iP) - B.EDOT * sE) * iom;
             break;
         case PINT_B_PB: dE = TWO_PI * ((B.PBDOT + B.XPBDOT) * tt0 * tt0 * iP2 * iP - tt0 * iP2) * iom; break;
         case PINT_B_PBDOT: case PINT_B_XPBDOT: dE = -PI_D * tt0 * tt0 * iP2 * iom; break;
@@ -1552,7 +1655,14 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
     // ---- binary (pulsar_binary.py:457, acc_delay = delay so far) ----
     BinState B;
     B.status = 0;
-    if (BIN == 1 || BIN == 3) {
+    if (BIN >= PINT_BLK_FB_ELL1) {  // the FBn orbit's builds (block kinds PINT_BLK_FB_*)
+        if (BIN == PINT_BLK_FB_ELL1) ell1_setup<false, false, true>(S, P, C, t.tdb, delay, B);
+        if (BIN == PINT_BLK_FB_ELL1H) ell1_setup<true, false, true>(S, P, C, t.tdb, delay, B);
+        if (BIN == PINT_BLK_FB_DD) ddm_setup<DDV_DD, true>(S, P, C, t.tdb, delay, B);
+        if (BIN == PINT_BLK_FB_BT) bt_setup<true>(S, P, C, t.tdb, delay, B);
+        delay += B.delay;
+        if (B.status) o.status = B.status;
+    } else if (BIN == 1 || BIN == 3) {
         ell1_setup<BIN == 3>(S, P, C, t.tdb, delay, B);
         delay += B.delay;
     } else if (BIN == 8) {
@@ -1591,6 +1701,8 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
         Ell1Grad eg;
         if (BIN == 1 || BIN == 3) ell1_grad<BIN == 3>(B, eg);
         if (BIN == 8) ell1_grad<false, true>(B, eg);
+        if (BIN == PINT_BLK_FB_ELL1) ell1_grad<false>(B, eg);
+        if (BIN == PINT_BLK_FB_ELL1H) ell1_grad<true>(B, eg);
         for (int u = 0; u < nrun; u++) {
             const ColRun R = runs[u];
             if (R.kind != PINT_COL_BIN) continue;
@@ -1605,6 +1717,9 @@ PD void eval_toa(const pint_spec_t& S, const double* P, const InstConst& C, cons
                 if (BIN == 6) d = ddm_deriv<DDV_DDS>(B, pid);
                 if (BIN == 7) d = ddm_deriv<DDV_DDH>(B, pid);
                 if (BIN == 8) d = ell1k_deriv(B, eg, pid);
+                if (BIN == PINT_BLK_FB_ELL1 || BIN == PINT_BLK_FB_ELL1H) d = ell1_deriv_fb(B, eg, pid);
+                if (BIN == PINT_BLK_FB_DD) d = ddm_deriv<DDV_DD, true>(B, pid);
+                if (BIN == PINT_BLK_FB_BT) d = bt_deriv<true>(B, pid);
                 colp[r] = chain * d * bin_unit_factor(pid);
             }
         }

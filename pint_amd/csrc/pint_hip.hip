@@ -6019,7 +6019,7 @@ struct pint_ctx {
     int eval_merge = 0;  // bit 0: one k_eval_mix launch without M, bit 1: with M, bit 2: also for a
                          // batch of one model (PINT_EVAL_MERGE)
     int nblk = 0;
-    int blk_off[PINT_NBIN + 1] = {0};  // block ranges per binary model (PINT_BIN_*)
+    int blk_off[PINT_NBLK + 1] = {0};  // block ranges per block kind (PINT_BIN_*, then PINT_BLK_FB_*)
     long tot_table = 0, tot_rows = 0, tot_m = 0, tot_g = 0, tot_s = 0, tot_c = 0, tot_out = 0, tot_cv = 0;
     int lazy = 0;
     int blocked_solve = 1;  // k_solve_blk (MFMA, blocked) vs the column-by-column k_solve
@@ -6903,6 +6903,17 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
         return -PINT_E_INVALID;
     }
     if (spec->binary < 0 || spec->binary >= PINT_NBIN) { ctx->err = "unsupported binary model"; return -PINT_E_INVALID; }
+    if (spec->rsv_[2] != 0) {  // the FBn block (PINT_SPEC_NFB / PINT_SPEC_O_FB)
+        const int nfb = PINT_SPEC_NFB(*spec), o_fb = PINT_SPEC_O_FB(*spec);
+        if (nfb < 1 || nfb > PINT_MAX_FB) { ctx->err = "FBn block: the number of terms is outside 1..PINT_MAX_FB"; return -PINT_E_INVALID; }
+        if (o_fb < 0 || o_fb + 2 * nfb > spec->tstride) { ctx->err = "FBn block: table slot outside the table"; return -PINT_E_INVALID; }
+        if (spec->binary != PINT_BIN_ELL1 && spec->binary != PINT_BIN_ELL1H && spec->binary != PINT_BIN_DD &&
+            spec->binary != PINT_BIN_BT) {
+            ctx->err = "FBn block: the model has no binary with an FBn orbit (ELL1, ELL1H, DD, BT)";
+            return -PINT_E_INVALID;
+        }
+        if (spec->o_bin[PINT_B_PB] >= 0) { ctx->err = "FBn block: the model has a PB slot too"; return -PINT_E_INVALID; }
+    }
     if (spec->binary == PINT_BIN_ELL1H &&
         (spec->ell1h < 1 || spec->ell1h > 3 || (spec->ell1h == 2 && (spec->nharms < 3 || spec->nharms > 64)))) {
         ctx->err = "bad ELL1H Shapiro form";
@@ -7386,7 +7397,7 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     long toff = 0, roff = 0, moff = 0, goff = 0, soff = 0, coff = 0, out = 0, cvoff = 0, eoff = 0, epoff = 0;
     long sdoff = 0, ddoff = 0;
     int max_nep = 0, max_ndc = 0;
-    std::vector<int> bti[PINT_NBIN], btr[PINT_NBIN];
+    std::vector<int> bti[PINT_NBLK], btr[PINT_NBLK];
     std::vector<int> rbi;
     int maxK = 0, maxN = 0;
     for (int k = 0; k < ninst; k++) {
@@ -7634,6 +7645,9 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
         toff += ph.spec.tstride;
         int bt = ph.spec.binary;
         if (bt < 0 || bt >= PINT_NBIN) { ctx->err = "bad binary model"; return PINT_E_INVALID; }
+        if (PINT_SPEC_NFB(ph.spec) > 0)  // the FBn orbit: its own block kind, so its own build and launch
+            bt = bt == PINT_BIN_ELL1 ? PINT_BLK_FB_ELL1
+                                     : (bt == PINT_BIN_DD ? PINT_BLK_FB_DD : (bt == PINT_BIN_ELL1H ? PINT_BLK_FB_ELL1H : PINT_BLK_FB_BT));
         if (ctx->efz) {  // EF_ROWS rows per block (+ row 0 and the TZR row on its last lanes)
             I.eb0 = ebn;
             I.neb = std::max(1, (ph.n + EF_ROWS - 1) / EF_ROWS);
@@ -7688,12 +7702,12 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     ctx->max_nep = max_nep;
     ctx->max_ndc = max_ndc;
     std::vector<int> bi, br;
-    for (int t = 0; t < PINT_NBIN; t++) {
+    for (int t = 0; t < PINT_NBLK; t++) {
         ctx->blk_off[t] = (int)bi.size();
         bi.insert(bi.end(), bti[t].begin(), bti[t].end());
         br.insert(br.end(), btr[t].begin(), btr[t].end());
     }
-    ctx->blk_off[PINT_NBIN] = (int)bi.size();
+    ctx->blk_off[PINT_NBLK] = (int)bi.size();
     ctx->nblk = ctx->blk_off[3];  // k_eval_mix covers the isolated, ELL1 and DD blocks
     HIPCHK(cmalloc((void**)&ctx->d_inst, sizeof(InstDev) * ninst));
     HIPCHK(h2d(ctx->d_inst, ctx->inst.data(), sizeof(InstDev) * ninst, nullptr, true));
@@ -8081,7 +8095,7 @@ int pint_eval(pint_ctx* ctx, int want_M) {
     // a spin-only grid's first evaluation with the design matrix: the shared head, then each
     // point's spin part
     const bool spin_pass = want_M && ctx->spin_grid && ctx->tables_fresh && ctx->spin_eval && rs.tables == nullptr &&
-                           !ctx->efz && ctx->d_shr && ctx->blk_off[PINT_NBIN] == ctx->blk_off[1];
+                           !ctx->efz && ctx->d_shr && ctx->blk_off[PINT_NBLK] == ctx->blk_off[1];
     if (ctx->d_swg) {  // SolarWindDispersion: the rows' geometry at these constants, read by the evaluation
         // (the shared head reads the first point's rows only)
         hipLaunchKernelGGL(k_sw_geom, dim3(spin_pass ? 1 : ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream,
@@ -8130,9 +8144,10 @@ int pint_eval(pint_ctx* ctx, int want_M) {
         HIPCHK(hipGetLastError());
     }
     // one launch per binary model, back to back on the stream: all models without the merged
-    // launch; ELL1H/BT/DDK/DDS/DDH/ELL1k always (they stay out of k_eval_mix so its register set, which
-    // every block of the merged launch carries, is not raised by the rarer models)
-    for (int t = spin_pass ? PINT_NBIN : (mix ? 3 : 0); t < PINT_NBIN; t++) {
+    // launch; ELL1H/BT/DDK/DDS/DDH/ELL1k and the FBn orbits' block kinds always (they stay out of
+    // k_eval_mix so its register set, which every block of the merged launch carries, is not raised
+    // by the rarer models)
+    for (int t = spin_pass ? PINT_NBLK : (mix ? 3 : 0); t < PINT_NBLK; t++) {
         int nb = ctx->blk_off[t + 1] - ctx->blk_off[t];
         if (nb == 0) continue;
         const int* bi = ctx->d_blk_inst + ctx->blk_off[t];
@@ -8161,7 +8176,11 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                 case 5: PINT_EVAL_LAUNCH(1, 5); break;
                 case 6: PINT_EVAL_LAUNCH(1, 6); break;
                 case 7: PINT_EVAL_LAUNCH(1, 7); break;
-                default: PINT_EVAL_LAUNCH(1, 8); break;
+                case 8: PINT_EVAL_LAUNCH(1, 8); break;
+                case PINT_BLK_FB_ELL1: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_ELL1); break;
+                case PINT_BLK_FB_DD: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_DD); break;
+                case PINT_BLK_FB_ELL1H: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_ELL1H); break;
+                default: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_BT); break;
             }
         } else {
             switch (t) {
@@ -8173,7 +8192,11 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                 case 5: PINT_EVAL_LAUNCH(0, 5); break;
                 case 6: PINT_EVAL_LAUNCH(0, 6); break;
                 case 7: PINT_EVAL_LAUNCH(0, 7); break;
-                default: PINT_EVAL_LAUNCH(0, 8); break;
+                case 8: PINT_EVAL_LAUNCH(0, 8); break;
+                case PINT_BLK_FB_ELL1: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_ELL1); break;
+                case PINT_BLK_FB_DD: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_DD); break;
+                case PINT_BLK_FB_ELL1H: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_ELL1H); break;
+                default: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_BT); break;
             }
         }
 #undef PINT_EVAL_LAUNCH

@@ -246,8 +246,21 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
                    "DDK": L.BIN_DDK, "DDS": L.BIN_DDS, "DDH": L.BIN_DDH, "ELL1k": L.BIN_ELL1K}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
+    # the FBn orbit: FB0 ... FB{nfb-1} in one contiguous block of dd pairs, ascending, described by
+    # the reserve word rsv_[2] (PINT_SPEC_NFB / PINT_SPEC_O_FB); PB then has no slot
+    fbs = [n for n in model.fb_terms() if model[n].value is not None] if model.binary else []
+    fb_cols = {}
+    if fbs:
+        if len(fbs) > L.MAX_FB:
+            raise NotImplementedError(f"more than {L.MAX_FB} FBn terms (PINT_MAX_FB)")
+        spec.rsv_[2] = (len(fbs) << 24) | (pos + 1)
+        for k, n in enumerate(fbs):
+            place(n)
+            fb_cols[n] = (L.COL_BIN, L.B_FB0 + k)
     if model.binary:
         for n, pid in BIN_IDS.items():
+            if fbs and n == "PB":
+                continue
             if n in model and model[n].kind != "func":  # (DDS's SINI, DDH's SINI / M2: derived on the device)
                 if pid < L.B_NPAR:
                     spec.o_bin[pid] = place(n)
@@ -269,7 +282,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         if model.binary == "DDH" and not (model.STIGMA.value is not None and float(model.STIGMA.value) > 0):
             # (the reference divides by STIGMA^3 and goes on with inf or a TypeError)
             raise ValueError(f"DDH needs STIGMA > 0 (STIGMA is {model.STIGMA.value}): M2 = H3 / STIGMA^3")
-        need = ["PB", "A1", "TASC" if model.binary in ("ELL1", "ELL1H", "ELL1k") else "T0"]
+        need = ["FB0" if fbs else "PB", "A1", "TASC" if model.binary in ("ELL1", "ELL1H", "ELL1k") else "T0"]
         for n in need:
             if n not in model or model[n].value is None:
                 raise ValueError(f"binary parameter {n} missing")
@@ -299,6 +312,7 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
             kind_of[nm] = (kk, 0)
     kind_of.update(glitch_cols)
     kind_of.update(wx_cols)
+    kind_of.update(fb_cols)
     # (later groups first, so that an earlier group wins a shared name, as the if-chain did)
     for group, kk in ((dmjumps, L.COL_ZERO), (jumps, L.COL_JUMP), (fds, L.COL_FD), (dmx, L.COL_DMX),
                       (dms, L.COL_DM), (F, L.COL_F)):

@@ -258,6 +258,7 @@ _ALIASES = {
     "RA": "RAJ", "DEC": "DECJ", "LAMBDA": "ELONG", "BETA": "ELAT", "PMLAMBDA": "PMELONG",
     "PMBETA": "PMELAT", "E": "ECC", "ECCDOT": "EDOT", "XDOT": "A1DOT", "T2EFAC": "EFAC",
     "T2EQUAD": "EQUAD", "TNECORR": "ECORR", "SOLARN0": "NE_SW", "NE1AU": "NE_SW", "CLK": "CLOCK", "PSRJ": "PSR", "PSRB": "PSR", "VARSIGMA": "STIGMA", "STIG": "STIGMA",
+    "FB": "FB0",
 }
 
 _PREFIX = {  # prefix params: regex -> (component, units template, long_double)
@@ -267,6 +268,8 @@ _PREFIX = {  # prefix params: regex -> (component, units template, long_double)
     r"^DMXR1_(\d+)$": ("DispersionDMX", "d", True),
     r"^DMXR2_(\d+)$": ("DispersionDMX", "d", True),
     r"^FD(\d+)$": ("FD", "s", False),
+    # the orbital frequency and its derivatives (pulsar_binary.py:192-205): longdouble, 1 / s^(n+1)
+    r"^FB(\d+)$": ("Binary", "1 / s^{n+1}", True),
     # Glitch (glitch.py:56-124): the epoch an MJD, the rest float64 in the reference's units
     r"^GLEP_(\d+)$": ("Glitch", "d", True),
     r"^GLPH_(\d+)$": ("Glitch", "pulse phase", False),
@@ -328,7 +331,7 @@ def make_param(name: str) -> Optional[Param]:
         if m:
             idx = int(m.group(1))
             kind = "mjd" if name.startswith(("DMXR", "GLEP_")) else "float"
-            u = units.replace("{n}", str(idx))
+            u = units.replace("{n+1}", str(idx + 1)).replace("{n}", str(idx))
             if name == "F0":
                 u = "Hz"
             if name.startswith(("DM", "CM")) and not name.startswith(("DMX", "DMWX", "CMWX")) and idx == 0:

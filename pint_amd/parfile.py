@@ -239,18 +239,18 @@ _ORDER = {
     "astrometry_ecl": ["ELONG", "ELAT", "PMELONG", "PMELAT", "PX", "ECL", "POSEPOCH"],
     "AbsPhase": ["TZRMJD", "TZRSITE", "TZRFRQ"],
     "SolarWindDispersion": ["NE_SW", "SWM"],
-    "DD": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "SINI", "A0", "B0", "GAMMA",
+    "DD": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "SINI", "FB0", "A0", "B0", "GAMMA",
            "DR", "DTH"],
-    "ELL1": ["PB", "PBDOT", "A1", "A1DOT", "M2", "SINI", "TASC", "EPS1", "EPS2", "EPS1DOT", "EPS2DOT"],
+    "ELL1": ["PB", "PBDOT", "A1", "A1DOT", "M2", "SINI", "FB0", "TASC", "EPS1", "EPS2", "EPS1DOT", "EPS2DOT"],
     "DDK": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "A0", "B0", "GAMMA",
             "DR", "DTH", "KIN", "KOM", "K96"],
-    "BT": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "GAMMA"],
+    "BT": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "FB0", "GAMMA"],
     "DDS": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "M2", "A0", "B0", "GAMMA", "DR",
             "DTH", "SHAPMAX"],
     "DDH": ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "A0", "B0", "GAMMA", "DR", "DTH",
             "H3", "STIGMA"],
     "ELL1k": ["PB", "PBDOT", "A1", "A1DOT", "M2", "SINI", "TASC", "EPS1", "EPS2", "OMDOT", "LNEDOT"],
-    "ELL1H": ["PB", "PBDOT", "A1", "A1DOT", "TASC", "EPS1", "EPS2", "EPS1DOT", "EPS2DOT", "H3", "H4", "STIGMA",
+    "ELL1H": ["PB", "PBDOT", "A1", "A1DOT", "FB0", "TASC", "EPS1", "EPS2", "EPS1DOT", "EPS2DOT", "H3", "H4", "STIGMA",
               "NHARMS"],
     "PLRedNoise": ["RNAMP", "RNIDX", "TNREDAMP", "TNREDGAM", "TNREDC"],
     "PLDMNoise": ["TNDMAMP", "TNDMGAM", "TNDMC"],

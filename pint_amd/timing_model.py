@@ -57,6 +57,10 @@ DDH_PARAMS = [n for n in DD_PARAMS if n not in ("M2", "SINI")] + ["H3", "STIGMA"
 ELL1K_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "M2", "SINI", "TASC", "EPS1", "EPS2", "OMDOT", "LNEDOT"]
 ELL1K_REMOVED = ("EPS1DOT", "EPS2DOT", "EDOT")
 BINARIES = ("ELL1", "DD", "ELL1H", "BT", "DDK", "DDS", "DDH", "ELL1k")
+# the models whose orbit may be given by FB0 ... FBn (OrbitFBX, binary_orbits.py:158-239); the other
+# four are variants of the same two device bodies and would each add two evaluation builds
+FBX_BINARIES = ("ELL1", "ELL1H", "DD", "BT")
+FB_NAME = re.compile(r"^FB(\d+)$")
 BT_PARAMS = ["PB", "PBDOT", "A1", "A1DOT", "ECC", "EDOT", "T0", "OM", "OMDOT", "GAMMA"]
 BIN_IDS = {"PB": 0, "PBDOT": 1, "XPBDOT": 2, "A1": 3, "A1DOT": 4, "ECC": 5, "EDOT": 6, "T0": 7, "OM": 8,
            "OMDOT": 9, "M2": 10, "SINI": 11, "GAMMA": 12, "DR": 13, "DTH": 14, "A0": 15, "B0": 16,
@@ -268,6 +272,27 @@ class TimingModel:
 
     def dmx_params(self) -> List[str]:
         return self.prefix_list(r"^DMX_(\d+)$")
+
+    def fb_terms(self) -> List[str]:
+        """FB0, FB1, ... in ascending index: the FBn parameters the model carries ([] for the
+        period form; they exist only when the par file names one)."""
+        return self.prefix_list(r"^FB(\d+)$")
+
+    def pb(self):
+        """PulsarBinary.pb at the reference epoch (pulsar_binary.py:566-625): the binary period and
+        its uncertainty in days, from PB, or from 1 / FB0 (the uncertainty to first order,
+        sigma_FB0 / FB0^2) when the orbit is given by FBn; the uncertainty is None when it is unset
+        or zero."""
+        if not self.binary:
+            raise AttributeError("the model has no binary component")
+        if "PB" in self._params and self.PB.value is not None:
+            s = self.PB.uncertainty_value
+            return LD(self.PB.value), (float(s) if s else None)
+        if "FB0" in self._params and self.FB0.value is not None:
+            f = LD(self.FB0.value)
+            s = self.FB0.uncertainty_value
+            return 1 / f / LD(86400), (float(LD(s) / f / f / LD(86400)) if s else None)
+        raise AttributeError("Neither PB nor FB0 is present in the timing model.")
 
     def fd_terms(self) -> List[str]:
         return self.prefix_list(r"^FD(\d+)$")
@@ -508,6 +533,16 @@ class TimingModel:
             e = float(self.ECC.value or 0.0)
             if not (0 <= e < 1):
                 raise ValueError("Eccentricity should be in the range of [0,1).")
+        if self.binary and "PB" in self._params and self.PB.value is not None:
+            # PulsarBinary.validate (pulsar_binary.py:311-324), for a model with FBn lines (the period
+            # form keeps what it did: its PB is checked when the layout is built)
+            fb0 = self._params.get("FB0")
+            if fb0 is not None and self.PB.value <= 0:
+                raise ValueError(f"Binary period PB must be non-negative ({self.PB.value} d)")
+            if fb0 is not None and fb0.value is not None:
+                raise ValueError("Model cannot have values for both FB0 and PB")
+        if self.binary and "FB0" in self._params and self.FB0.value is not None and self.FB0.value <= 0:
+            raise ValueError(f"Binary frequency FB0 must be non-negative ({float(self.FB0.value)} 1 / s)")
         if self.binary == "DDS" and self.SHAPMAX.value is not None and not self.SHAPMAX.value > -np.log(2):
             # BinaryDDS.validate (binary_dd.py:200-208)
             raise ValueError(f"SHAPMAX must be > -log(2) ({self.SHAPMAX.value})")
@@ -672,6 +707,15 @@ def get_model(parfile) -> TimingModel:
     if binary not in (None,) + BINARIES:
         raise NotImplementedError(f"BINARY {binary} is outside the supported hot path ({', '.join(BINARIES)})")
     model.binary = binary
+    # FB0 (alias FB), FB1, ...: the binary's orbit by orbital frequency.  The parameters exist only
+    # when the par file names one (the reference carries an unset FB0 on every binary model)
+    fb_lines = [n for n in names if n == "FB" or FB_NAME.match(n)]
+    if fb_lines and binary not in FBX_BINARIES and binary is not None:
+        raise NotImplementedError(f"BINARY {binary} with an FB0 ... FBn orbit ({fb_lines[0]}) is outside the "
+                                  f"supported hot path (FB0 with {', '.join(FBX_BINARIES)})")
+    if fb_lines and binary is None:
+        raise TimingModelError(f"Parameter {fb_lines[0]} is recognized, but not used in the current timing model "
+                               "(it has no binary component).")
     has_eq = any(n in ("RAJ", "RA") for n in names)
     has_ecl = any(n in ("ELONG", "LAMBDA") for n in names)
     # defaults the reference components create (values 0 / None)
@@ -714,6 +758,9 @@ def get_model(parfile) -> TimingModel:
     elif binary == "BT":  # binary_bt.py:38-69: no M2/SINI, GAMMA 0, rates 0
         defaults += [(n, 0.0) for n in BT_PARAMS if n != "T0"]
         defaults += [("T0", None)]
+    if fb_lines:  # FB0 where the reference's PulsarBinary declares it, after SINI (pulsar_binary.py:192)
+        at = max(i for i, (n, _) in enumerate(defaults) if n in ("SINI", "OMDOT")) + 1
+        defaults.insert(at, ("FB0", None))
     for n, v in defaults:
         if n in model:
             continue
@@ -773,7 +820,7 @@ def get_model(parfile) -> TimingModel:
         if name not in model:
             p = P.make_param(name)
             if p is None:
-                if name in ("FB0", "SWP", "H3", "STIGMA"):
+                if name in ("SWP", "H3", "STIGMA"):
                     continue
                 if wavex_rx.match(name):  # (only the four-digit index is a name: model_builder warns and goes on)
                     import warnings
@@ -805,6 +852,21 @@ def get_model(parfile) -> TimingModel:
                     p.set_uncertainty_from_string(l.fields[2])
             else:
                 p.set_uncertainty_from_string(fl)
+    if fb_lines:
+        # PulsarBinary.setup (pulsar_binary.py:217-228) and OrbitFBX (binary_orbits.py:164-173).  With
+        # FBn the model has PB unset unless the par file gives it (validate then refuses both).
+        if "PB" not in names:
+            model["PB"].value = None
+        fbs = {int(FB_NAME.match(n).group(1)): model[n] for n in model.fb_terms()}
+        if any(p.value is not None for p in fbs.values()):
+            if fbs[0].value is None:
+                raise ValueError("Some FBn parameters are set but FB0 is not.")
+            indices = {k for k, p in fbs.items() if p.value is not None}
+            if indices != set(range(len(indices))):
+                # (the reference means to raise this but never does: every FBn is in the list its
+                # OrbitFBX is given, so the check sees no index, and the sums then stop at the first
+                # missing one, silently dropping the terms above a gap)
+                raise ValueError(f"Indices must be 0 up to some number k without gaps but are {indices}.")
     model.setup_glitches()
     # components present
     comps = set()
