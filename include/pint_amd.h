@@ -521,7 +521,9 @@ int pint_check_step(pint_ctx *ctx, int slot);
 /* PINT_OPT_WBFIT = 1: pint_fit_step adds the wideband DM rows (pint_set_wideband) of every
  * compact-layout instance to its normal equations (WidebandTOAFitter.fit_toas,
  * fitter.py:2465-2637: design matrix [M_toa | F; M_dm | 0], residuals [r; pp_dm - DM]);
- * default 0. */
+ * default 0.  With it set pint_fit_step returns PINT_E_INVALID, before any launch, when the
+ * design matrix is in the full layout (pint_eval want_M = 1) or a pulsar with wideband data is
+ * not on the compact DMX layout (pint_fit_layout): the DM rows would be left out. */
 #define PINT_OPT_WBFIT 6
 /* PINT_OPT_COV_DEFER (default 1, env PINT_COV_DEFER): the covariance of the DMX-eliminated
  * solve is formed by pint_read_step (k_cov_dmx, several workgroups per instance, on the copy

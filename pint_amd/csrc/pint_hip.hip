@@ -8365,11 +8365,24 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
     if (ctx->r2_pending && !can_defer_r2(ctx)) flush_r2(ctx);  // (a kernel below reads d_rt)
     const GvResid gvr{ctx->d_rp, ctx->d_ftay, ctx->d_rpart, ctx->r2_pending ? 1 : 0, ctx->efz ? ctx->d_epart : nullptr};
     if (ctx->wbfit) {
+        // k_wb_gram adds the DM rows to the compact normal equations only: a design matrix in
+        // the full layout, or a wideband pulsar that stays on it (fewer than 8 free DMX bins, a
+        // TOA in two free bins, ECORR epochs across bins), is refused instead of taking a
+        // TOA-only step
+        if (!ctx->m_compact) {
+            ctx->err = "wideband fit: the DM rows need the compact fit layout (pint_eval with want_M = 2)";
+            return PINT_E_INVALID;
+        }
         // k_wb_gram carries at most WB_MAXC free DM-type columns (DM Taylor terms + DMJUMPs):
         // refuse more instead of leaving the extra columns without their DM rows
         for (int pi : ctx->upsr) {
             const pint_spec_t& sp = ctx->psrs[pi].spec;
             if (!ctx->psrs[pi].dev.wb) continue;
+            if (!ctx->psrs[pi].dev.dsplit) {
+                ctx->err = "wideband fit: a pulsar with wideband DM data is not on the compact DMX layout "
+                           "(>= 8 free DMX bins, no TOA in two free bins, every ECORR epoch within one bin)";
+                return PINT_E_INVALID;
+            }
             int m = 0;
             for (int c = 0; c < sp.ncol; c++)
                 m += (sp.col_kind[c] == PINT_COL_DM || sp.col_kind[c] == PINT_COL_ZERO || sp.col_kind[c] == PINT_COL_NESW);

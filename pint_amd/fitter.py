@@ -151,7 +151,8 @@ class BatchFit:
             for lay in {id(l): l for l in layouts}.values():
                 if self.s.fit_layout(lay)[0] != 1:
                     raise NotImplementedError("wideband fits on the device need the compact DMX layout (>= 8 "
-                                              "free DMX bins, no TOA in two free bins, no ECORR)")
+                                              "free DMX bins, no TOA in two free bins, every ECORR epoch within "
+                                              "one bin)")
                 self.s.set_wideband(lay)
             self.s.set_wbfit(True)
 
@@ -774,7 +775,8 @@ class WidebandTOAFitter(Fitter):
     noise-basis columns), the residuals [TOA residuals; pp_dm - DM] with the scaled TOA and
     DM errors.  On the device the DM rows only touch the DM-type columns and the residual of
     the normal equations (k_wb_gram, PINT_OPT_WBFIT); the rest is the GLS step.  Needs the
-    compact DMX layout (>= 8 free DMX bins, no TOA in two bins, no ECORR)."""
+    compact DMX layout (>= 8 free DMX bins, no TOA in two bins, every ECORR epoch within one
+    bin)."""
 
     def __init__(self, fit_data, model, fit_data_names=["toa", "dm"], track_mode=None, additional_args={}):
         toas = fit_data[0] if isinstance(fit_data, (list, tuple)) else fit_data

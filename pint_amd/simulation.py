@@ -188,6 +188,22 @@ def make_fake_toas_uniform(startMJD, endMJD, ntoas, model, freq=1400.0, obs="geo
                                       multi_freqs_in_epoch=multi_freqs_in_epoch, flags=flags, seed=seed)])[0]
 
 
+def attach_wideband(toas: TOAs, dm, dme, flags=None) -> TOAs:
+    """Make `toas` wideband in place: the DM measurements and their errors (pc/cm^3) as the
+    -pp_dm / -pp_dme flag columns TOAs.get_dms reads (repr strings: a float64 round-trips),
+    and any further flag columns (one value per TOA) for mask parameters to select on."""
+    dm, dme = np.asarray(dm, dtype=np.float64), np.asarray(dme, dtype=np.float64)
+    if dm.shape != (toas.ntoas,) or dme.shape != (toas.ntoas,):
+        raise ValueError("one DM and one DM error per TOA")
+    cols = {k: list(v) for k, v in toas.flag_columns.items()}
+    for k, v in (flags or {}).items():
+        cols[k] = [str(x) for x in v]
+    cols["pp_dm"] = [repr(float(x)) for x in dm]
+    cols["pp_dme"] = [repr(float(x)) for x in dme]
+    toas.flag_columns = cols
+    return toas
+
+
 def pta_par(seed: int, binary: str = "", ndmx: int = 100, nmodes: int = 30) -> str:
     """Synthetic PTA pulsar template of SURVEY.md §8(d) C5 (pulsar i uses seed i):
     sky position uniform on the sphere, PM ~ N(0, 5 mas/yr), PX 1 mas, F0 ~ U[100, 700] Hz,

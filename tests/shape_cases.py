@@ -6,6 +6,12 @@ and adding fitted WaveX amplitudes at half-integer multiples of 1 / Tspan above 
 band (not degenerate with the red-noise basis at the integer multiples); predict_plan repeats
 the dispatch arithmetic of pint_set_instances / pint_fit_step (pint_hip.hip) for a batch of
 that one pulsar and returns the plan Session.last_plan() must report.
+
+The wideband sweep (wb_cases.py, test_wideband_sweep.py) uses the same Case with its wideband
+fields set: free DM Taylor terms, DMJUMPs and NE_SW beside the ntim timing columns (ndense),
+frozen DMX bins and DMJUMPs, a bin of one TOA, the TOA order; bin_rows / free_rows map TOAs to
+the model's bins and to the compact DMX columns, and predict_plan adds k_dmx, k_ecorr_dmx and
+k_wb_gram to the plan.  Cases without those fields predict what they did before.
 """
 from dataclasses import dataclass, replace
 
@@ -48,14 +54,35 @@ class Case:
     postfit: bool = False  # also the post-fit chi2 of the device's own residuals (the fused Woodbury dots)
     refused: bool = False  # pint_fit_step must refuse the batch before launching
     ecorr: bool = False   # an ECORR on every TOA (the "e" TOA sets: several frequencies per epoch)
+    # wideband cases (wb_cases.py; test_wideband_sweep.py): DM-type columns beside the ntim others
+    wb: bool = False         # wideband DM data on the TOAs, the DM rows in the fit step
+    dm_free: tuple = ()      # free DM Taylor terms, of "DM", "DM1", "DM2"
+    ndmjump: int = 0         # DMJUMPs of the model
+    dmj_frozen: tuple = ()   # ... of which frozen (0-based, with non-zero values)
+    dmx_frozen: tuple = ()   # frozen DMX bins (0-based, with non-zero values)
+    dm12_zero: bool = False  # DM1 = DM2 = 0
+    dmefac: bool = False     # DMEFAC 1.3 and a DMEQUAD on one flag value
+    order: str = ""          # TOA order: "" (by time), "reverse", "shuffle"
+    one_toa: bool = False    # bin 2 shrunk onto one TOA (its other TOAs lie in no bin)
+    nesw: bool = False       # NE_SW free
 
     @property
     def ndmx_free(self):
-        return self.ndmx if self.dmx_free else 0
+        return self.ndmx - len(self.dmx_frozen) if self.dmx_free else 0
+
+    @property
+    def m_dm(self):
+        """Free dense DM-type columns: DM Taylor terms, DMJUMPs, NE_SW (k_wb_gram's m)."""
+        return len(self.dm_free) + self.ndmjump - len(self.dmj_frozen) + int(self.nesw)
+
+    @property
+    def ndense(self):
+        """Columns outside the DMX bins: the ntim timing columns and the DM-type ones."""
+        return self.ntim + self.m_dm
 
     @property
     def ncol(self):
-        return self.ntim + self.ndmx_free
+        return self.ndense + self.ndmx_free
 
     @property
     def K(self):
@@ -90,6 +117,40 @@ def par_of(c: Case) -> str:
         par = "\n".join(l for l in par.split("\n") if not l.startswith("TNRed")) + "\n"
     if c.ecorr:
         par += "ECORR -f fake 0.5\n"
+    if c.wb:
+        par = wideband_par(c, par)
+    return par
+
+
+# DMJUMP selectors of the wideband cases, in the model's order (wb_cases.wb_flags writes the
+# columns): -fe has four values, -be three, -gp two, so no set of them sums to the DM column,
+# and TOAs with -fe A -be X, -fe A -gp G, ... lie in two or three masks
+DMJ_KEYS = (("-fe", "A"), ("-be", "X"), ("-fe", "B"), ("-be", "Y"), ("-gp", "G"))
+DMJ_VALUES = (1.2e-3, -7e-4, 4e-4, -3e-4, 9e-4)
+NE_SW = 7.9
+WB_DM = (3.1, 1e-4, 1e-5)  # DM (one ulp 4.4e-16: the DM residuals' rounding stays below the Gram's bar), DM1, DM2
+
+
+def wideband_par(c: Case, par: str) -> str:
+    """pta_par's text with the wideband cases' changes: DM, DM1, DM2 values, the one-TOA bin's
+    range, DMJUMPs, DMEFAC / DMEQUAD on -fe B, and NE_SW (SWM 0)."""
+    dm = WB_DM if not c.dm12_zero else (WB_DM[0], 0.0, 0.0)
+    rng = dmx_ranges(c)
+    out = []
+    for l in par.split("\n"):
+        w = l.split()
+        if w and w[0] in ("DM", "DM1", "DM2"):
+            l = f"{w[0]} {dm[('DM', 'DM1', 'DM2').index(w[0])]!r}"
+        elif w and w[0].startswith(("DMXR1_", "DMXR2_")):
+            l = f"{w[0]} {rng[int(w[0][6:]) - 1][int(w[0][4]) - 1]:.5f}"
+        out.append(l)
+    par = "\n".join(out)
+    for (k, v), x in list(zip(DMJ_KEYS, DMJ_VALUES))[:c.ndmjump]:
+        par += f"DMJUMP {k} {v} {x!r}\n"
+    if c.dmefac:
+        par += "DMEFAC -fe B 1.3\nDMEQUAD -fe B 0.0002\n"
+    if c.nesw:
+        par += f"NE_SW {NE_SW!r}\nSWM 0\n"
     return par
 
 
@@ -102,8 +163,15 @@ def model_of(c: Case):
     if nwx:
         wavex_setup(m, TSPAN, freqs=wavex_freqs(nwx, c.nred))
         free += [n for n in m.params if n.startswith(("WXSIN_", "WXCOS_"))]
+    if c.wb:
+        if nwx or any(p in free for p in ("DM1", "DM2")):
+            raise ValueError("wideband cases: ntim <= 8 (no WaveX beside wideband data); DM terms by dm_free")
+        free += list(c.dm_free)
+        free += [n for k, n in enumerate(m.mask_params("DMJUMP")) if k not in c.dmj_frozen]
+        if c.nesw:
+            free.append("NE_SW")
     if c.dmx_free:
-        free += list(m.dmx_params())
+        free += [n for a, n in enumerate(m.dmx_params()) if a not in c.dmx_frozen]
     m.free_params = free
     return m
 
@@ -112,6 +180,45 @@ def dmx_rows(mjd, ndmx):
     """The DMX bin of every TOA (pta_par's ranges)."""
     edges = np.round(np.linspace(53000, 56652.01, ndmx + 1), 5)
     return np.clip(np.searchsorted(edges, np.asarray(mjd, dtype=np.float64), side="right") - 1, 0, ndmx - 1)
+
+
+def dmx_ranges(c):
+    """(DMXR1, DMXR2) of every bin of the case's model: pta_par's, bin 2 shrunk onto the first
+    TOA at or after its lower edge with one_toa (TOAs evenly spaced over MJD0..MJD1)."""
+    edges = np.round(np.linspace(53000, 56652.01, c.ndmx + 1), 5)
+    rng = [(float(edges[i]), float(edges[i + 1])) for i in range(c.ndmx)]
+    if c.one_toa:
+        n = int(c.toas[1:])
+        dt = TSPAN / (n - 1)
+        k = int(np.ceil((rng[2][0] - MJD0) / dt))
+        rng[2] = (round(MJD0 + (k - 0.4) * dt, 5), round(MJD0 + (k + 0.4) * dt, 5))
+    return rng
+
+
+def bin_rows(c, mjd):
+    """The model's DMX bin of every TOA (index among all bins), -1 outside every bin."""
+    mjd = np.asarray(mjd, dtype=np.float64)
+    out = np.full(len(mjd), -1)
+    for a, (r1, r2) in enumerate(dmx_ranges(c)):
+        sel = (mjd >= r1) & (mjd <= r2)
+        assert np.all(out[sel] < 0), "a TOA in two bins"
+        out[sel] = a
+    return out
+
+
+def free_rows(c, mjd):
+    """The compact DMX column (index among the free bins) of every TOA, -1 without one."""
+    if not (c.dmx_frozen or c.one_toa):
+        return dmx_rows(mjd, c.ndmx)
+    free = [a for a in range(c.ndmx) if a not in c.dmx_frozen]
+    col = np.full(c.ndmx + 1, -1)
+    col[free] = np.arange(len(free))
+    return col[bin_rows(c, mjd)]
+
+
+def rows_contiguous(drow, ndc):
+    """Every column's TOAs are one contiguous row range (dcontig)."""
+    return all(np.all(np.diff(np.flatnonzero(drow == a)) == 1) for a in range(ndc))
 
 
 def _pad16(k):
@@ -125,9 +232,11 @@ def gram_T(kp):
 
 def vgram_layout(c: Case, n, drow, nsplit):
     """(on the k_gram_v path, row tiles, DMX slots, LDS width) as pint_set_instances decides."""
-    if not (c.vgram and c.ndmx_free >= 8 and c.nred <= VTRIG // 2 - 1 and c.ntim + 1 <= VMAXR0):
+    if not (c.vgram and c.ndmx_free >= 8 and c.nred <= VTRIG // 2 - 1 and c.ndense + 1 <= VMAXR0):
         return 0, 0, 0, 0
-    wt, R, ndc = c.ntim + 1, 2 * c.nred, c.ndmx_free
+    if c.ecorr or not rows_contiguous(drow, c.ndmx_free):  # k_gram_v: no ECORR, contiguous bins
+        return 0, 0, 0, 0
+    wt, R, ndc = c.ndense + 1, 2 * c.nred, c.ndmx_free
     per = ((n + nsplit - 1) // nsplit + 3) // 4 * 4
     lo = [int(np.flatnonzero(drow == a)[0]) if np.any(drow == a) else 0 for a in range(ndc)]
     hi = [int(np.flatnonzero(drow == a)[-1]) + 1 if np.any(drow == a) else 0 for a in range(ndc)]
@@ -175,9 +284,9 @@ def vgram_layout(c: Case, n, drow, nsplit):
 
 
 def predict_plan(c: Case, n, mjd):
-    """The plan of pint_fit_step(c.mode) for a batch of this one pulsar (no wideband data, ECORR
-    on the full layout only, default options but those the case names), in Session.last_plan()'s
-    form."""
+    """The plan of pint_fit_step(c.mode) for a batch of this one pulsar (ECORR off the small
+    path; wideband DM rows with c.wb; default options but those the case names), in
+    Session.last_plan()'s form.  mjd: the TOAs' MJDs in the order they are uploaded."""
     plan = dict(gram_T=(), gram_v=(), solve="none", gram_ecorr=False, gram_s=False, greduce=False, dmx_rows=False,
                 dmx=False, ecorr_dmx=False, wb_gram=False, fuse_sigma=False, side_sigma=False, do_sigma=False,
                 schur=False, cov_deferred=False, nsplit=0, solve_dmx_waves=0, sigma_waves=0)
@@ -186,13 +295,14 @@ def predict_plan(c: Case, n, mjd):
     K, Kp = c.K, _pad16(c.K + 1)
     cmp = c.layout == "fit"
     dsplit = c.ndmx_free >= 8
-    Kd = c.ntim + 2 * c.nred
+    Kd = c.ndense + 2 * c.nred
     Kpd = _pad16(Kd + 1)
     nsplit = min(c.nsplit, max(1, (n + 63) // 64))
     plan["nsplit"] = nsplit
     vg = 0
     if dsplit:
-        vg, ntr, ns, kpv = vgram_layout(c, n, dmx_rows(mjd, c.ndmx), nsplit)
+        drow = free_rows(c, mjd)
+        vg, ntr, ns, kpv = vgram_layout(c, n, drow, nsplit)
     vgp = bool(cmp and vg)
     if vgp:
         C = kpv // 16
@@ -204,17 +314,22 @@ def predict_plan(c: Case, n, mjd):
         else:
             plan["gram_T"] = (gram_T(kp),)
         plan["dmx_rows"] = bool(cmp and dsplit)
+        # rows of a bin that are not contiguous: k_dmx gathers them (k_dmx_rows returns at once)
+        plan["dmx"] = bool(cmp and dsplit and not rows_contiguous(drow, c.ndmx_free))
     nep = bool(c.ecorr and c.mode == 1)  # the ECORR Schur partial: k_gram<T, ch, true> and one more part
-    if c.ecorr and (cmp or plan["gram_s"]):
-        raise NotImplementedError("ECORR cases: full layout, off the small path")
+    if c.ecorr and plan["gram_s"]:
+        raise NotImplementedError("ECORR cases: off the small path")
     plan["gram_ecorr"] = nep
+    # compact layout with ECORR (every epoch within one DMX column): its share of the DMX rows
+    plan["ecorr_dmx"] = bool(nep and plan["dmx_rows"])
+    plan["wb_gram"] = bool(c.wb and cmp)
     plan["greduce"] = nsplit + nep > 1 or vgp
     # the solve
     mode = c.mode
     kn = 2 * c.nred + 1 if mode == 1 else 0
     Ks, skip, dmx_ok = 0, 0, cmp
     if cmp and dsplit:
-        kd = c.ntim if mode == 0 else Kd
+        kd = c.ndense if mode == 0 else Kd
         nbd, nbk, nbs = (kd + 15) // 16, (c.ndmx_free + 15) // 16, (kn + 15) // 16
         blk = nbd * (nbd + 1) // 2 + nbd * nbk
         lds_x = 8 * (max(blk, nbs * (nbs + 1) // 2) * 256 + (5 * nbd + 6 * nbk) * 16)
