@@ -52,6 +52,9 @@ extern "C" {
 #define PINT_MAX_FDJUMP 64    /* FDJump parameters, and FDJumpDM parameters, per model: one 64-bit mask
                                  word per row and family                                               */
 #define PINT_FDJUMP_MAX_INDEX 20 /* the largest FD index p of FD{p}JUMP{q} (fdjump.py:12)                */
+#define PINT_MAX_PW 64        /* PiecewiseSpindown pieces per model (the glitch cap)                    */
+#define PINT_MAX_WAVE 128     /* Wave terms WAVE1 ... WAVEn per model                                   */
+#define PINT_MAX_IFUNC 1024   /* IFunc control points per model (tempo2's own limit is 1000)            */
 
 /* ---- per-TOA packed input (reference TOAs.table columns
  *      toa.py:2320 tdbld, :2385-2439 posvels, freq, error, mjd_float, pulse_number) ---- */
@@ -133,9 +136,19 @@ enum {
     PINT_COL_FDJUMP = 19,   /* FD{p}JUMP{q}: col_index = the parameter's place in pint_set_fdjump's block
                                (ascending p), also its bit in the row masks; d_delay_d_p = y^p on the
                                rows its mask selects, 0 elsewhere (fdjump.py:177-193)                  */
-    PINT_COL_FDJUMPDM = 20  /* FDJUMPDM{q}: col_index = the place in the FDJumpDM block and the mask bit;
+    PINT_COL_FDJUMPDM = 20, /* FDJUMPDM{q}: col_index = the place in the FDJumpDM block and the mask bit;
                                d_delay_d_p = -DMconst / bfreq^2 on the selected rows
                                (dispersion_model.py:877-884, :99-109)                                  */
+    PINT_COL_PW = 21        /* PWPH_ / PWF0_ / PWF1_ / PWF2_: col_index = 4 * piece + (0 PH, 1 F0, 2 F1, 3 F2),
+                               piece = the place in pint_set_phase_terms' block; -(1, dt, dt^2 / 2,
+                               dt^3 / 6) / F0 on the rows inside the piece's window, exactly 0 outside
+                               (piecewise.py:237-253)                                                 */
+};
+/* the parameters of one PiecewiseSpindown piece, in the order of its 7 table slots
+ * (piecewise.py:130-138 pwsol_prop) */
+enum {
+    PINT_PW_EP = 0, PINT_PW_START, PINT_PW_STOP, PINT_PW_PH, PINT_PW_F0, PINT_PW_F1, PINT_PW_F2,
+    PINT_PW_NPAR
 };
 /* the parameters of one glitch, in the order of its 7 table slots (glitch.py:130-138 glitch_prop) */
 enum {
@@ -347,6 +360,31 @@ int pint_set_chromatic(pint_ctx *ctx, int psr, int o_cm, int ncm, int o_cmwx, in
  * calling rule as pint_set_wavex; a model with neither component makes no call. */
 int pint_set_fdjump(pint_ctx *ctx, int psr, int o_fdj, int nfdj, const int32_t *fd_index, int use_log,
                     const uint64_t *mask, int o_fdjdm, int nfdjdm, const uint64_t *dmmask);
+/* PiecewiseSpindown, Wave and IFunc (piecewise.py, wave.py, ifunc.py) of pulsar `psr`: three
+ * phase components, each added to a row's phase at the row's total delay, described beside the
+ * spec like WaveX.
+ *   PiecewiseSpindown  npw (<= PINT_MAX_PW) pieces at table slot o_pw, PINT_PW_NPAR dd pairs per
+ *             piece in ascending index (PWEP, PWSTART, PWSTOP in MJD; PWPH, PWF0, PWF1, PWF2).  On
+ *             the rows with PWSTART <= tdb < PWSTOP (the TOA's own TDB, not the emission time) the
+ *             phase gains PWPH + dt (PWF0 + dt PWF1 / 2 + dt^2 PWF2 / 6), dt = (tdb - PWEP) 86400 s
+ *             - delay; overlapping pieces both add; columns PINT_COL_PW;
+ *   Wave      at o_wave the dd pairs of WAVEEPOCH (MJD) and WAVE_OM (rad / d), then nwave (<=
+ *             PINT_MAX_WAVE) pairs of doubles (a_k, b_k) in seconds, k = 1 ... nwave:
+ *             phase += F0 sum_k a_k sin(k b) + b_k cos(k b), b = WAVE_OM (tdb - WAVEEPOCH - delay / 86400 s);
+ *   IFunc     nifunc (<= PINT_MAX_IFUNC) control points (x_hi + x_lo MJD, non-decreasing; y s) and
+ *             the interpolation type sifunc: 2 linear between the points and constant outside them,
+ *             0 the reference's piecewise-constant form as it runs (ifunc.py:131-134: y_0 before
+ *             x_0, y_{n-1} from x_1 on, y_2 or at x_0 itself y_1 between; needs nifunc >= 3);
+ *             phase += F0 times(tdb - delay / 86400 s).  The library keeps device copies of the
+ *             three arrays and frees them with the pulsar.
+ * Nothing of Wave or IFunc is fittable.  None of the three registers a derivative with respect
+ * to the delay, so every other column is unchanged.  The TZR TOA is treated like any TOA.  A pass
+ * of its own (k_phase_terms, after k_wavex and k_fdjump, beside k_glitch); a batch without the
+ * components launches what it launched before.  Wideband DM data with any of them is refused.
+ * A bad count, slot, pointer, order or type returns PINT_E_INVALID and leaves the pulsar as it
+ * was.  Same calling rule as pint_set_wavex; a model with none of the three makes no call. */
+int pint_set_phase_terms(pint_ctx *ctx, int psr, int o_pw, int npw, int o_wave, int nwave, int sifunc, int nifunc,
+                         const double *ifunc_x_hi, const double *ifunc_x_lo, const double *ifunc_y);
 
 /* Bind `ninst` instances (grid points, PTA pulsars, trial states): inst_psr[k] is a
  * pulsar id; `tables` concatenates each instance's parameter table (spec.tstride doubles,

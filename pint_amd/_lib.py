@@ -21,13 +21,17 @@ B_FB0 = 29    # PINT_B_FB0: the column id of FBn is B_FB0 + n; the block: rsv_[2
 MAX_FB = 20   # PINT_MAX_FB
 BIN_NONE, BIN_ELL1, BIN_DD, BIN_ELL1H, BIN_BT, BIN_DDK, BIN_DDS, BIN_DDH, BIN_ELL1K = range(9)
 
-COL_OFFSET, COL_F, COL_LON, COL_LAT, COL_PMLON, COL_PMLAT, COL_PX, COL_DM, COL_DMX, COL_FD, COL_JUMP, COL_BIN, COL_ZERO, COL_NESW, COL_GLITCH, COL_WX, COL_DMWX, COL_CM, COL_CMWX, COL_FDJUMP, COL_FDJUMPDM = range(21)
+COL_OFFSET, COL_F, COL_LON, COL_LAT, COL_PMLON, COL_PMLAT, COL_PX, COL_DM, COL_DMX, COL_FD, COL_JUMP, COL_BIN, COL_ZERO, COL_NESW, COL_GLITCH, COL_WX, COL_DMWX, COL_CM, COL_CMWX, COL_FDJUMP, COL_FDJUMPDM, COL_PW = range(22)
 MAX_GLITCH = 64  # PINT_MAX_GLITCH
 GL_NPAR = 7      # PINT_GL_NPAR: GLEP, GLPH, GLF0, GLF1, GLF2, GLF0D, GLTD (col_index = 7 * glitch + which)
 MAX_WAVEX = 128  # PINT_MAX_WAVEX: harmonics per component (col_index = 2 * harmonic + (0 sin, 1 cos))
 MAX_CM = 16      # PINT_MAX_CM: ChromaticCM Taylor terms (col_index = the order)
 MAX_FDJUMP = 64  # PINT_MAX_FDJUMP: FDJump parameters, and FDJumpDM parameters, per model (one mask word per row)
 FDJUMP_MAX_INDEX = 20  # PINT_FDJUMP_MAX_INDEX: the largest FD index p of FD{p}JUMP (fdjump.py:12)
+MAX_PW = 64       # PINT_MAX_PW: PiecewiseSpindown pieces (col_index = 4 * piece + (0 PH, 1 F0, 2 F1, 3 F2))
+PW_NPAR = 7       # PINT_PW_NPAR: PWEP, PWSTART, PWSTOP, PWPH, PWF0, PWF1, PWF2 (one dd pair each)
+MAX_WAVE = 128    # PINT_MAX_WAVE: Wave terms
+MAX_IFUNC = 1024  # PINT_MAX_IFUNC: IFunc control points
 
 PINT_OK, PINT_E_INVALID, PINT_E_HIP, PINT_E_NOT_PD, PINT_E_KEPLER, PINT_E_PARAM, PINT_E_SIGMA = range(7)
 
@@ -186,6 +190,7 @@ def lib():
     L.pint_set_chromatic.argtypes = [vp] + [C.c_int] * 5
     L.pint_set_fdjump.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint64),
                                   C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    L.pint_set_phase_terms.argtypes = [vp] + [C.c_int] * 7 + [dptr] * 3
     L.pint_check.argtypes = [vp]
     L.pint_step_end.argtypes = [vp, C.POINTER(C.c_int)]
     L.pint_fit_step_enqueue.argtypes = [vp, C.c_int, C.c_int, C.c_double] + [dptr] * 8 + [C.POINTER(C.c_int)]
@@ -219,7 +224,7 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_noise_lnlike", "pint_noise_resids_dm", "pint_set_wideband", "pint_dm_resids", "pint_chi2_wls",
             "pint_apply_step_uniform", "pint_fit_step_apply", "pint_save_tables", "pint_restore_tables", "pint_read_norms",
             "pint_fit_step_enqueue", "pint_set_grid", "pint_add_pulsar_cols", "pint_pack_toas",
-            "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan"]
+            "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

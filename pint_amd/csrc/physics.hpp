@@ -1397,6 +1397,105 @@ PD void glitch_row_columns(const pint_spec_t& S, const double* P, dd tdb, double
     }
 }
 
+// PiecewiseSpindown (piecewise.py:181-253), Wave (wave.py:148-168) and IFunc (ifunc.py:113-148):
+// three more phase components at the row's total delay, in a pass of their own like the glitch
+// (k_phase_terms), for the glitch's reason: the evaluation's builds keep their registers.
+//
+// dt of one piece (its block B of PINT_PW_NPAR dd pairs) at a row, and whether the piece acts
+// there: PWSTART <= tdb < PWSTOP on the TOA's own TDB (get_dt_and_affected, :181-190: not the
+// emission time), compared in dd; dt = (tdb - PWEP) 86400 s - delay formed in dd (the epoch
+// difference is exact there) and rounded once.  A piece's phase and its columns call this one
+// function, so they take the same dt and the same decision.
+PD bool pw_dt(const double* B, dd tdb, double delay, double& dt) {
+    dt = dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(B, 2 * PINT_PW_EP)), DAYSEC), -delay));
+    // (a normalised dd has the sign of its high word)
+    return dd_sub(tdb, pdd(B, 2 * PINT_PW_START)).hi >= 0.0 && dd_sub(tdb, pdd(B, 2 * PINT_PW_STOP)).hi < 0.0;
+}
+// taylor_horner(dt, [PWPH, PWF0, PWF1, PWF2]) (:192-211) in double: after dt's one rounding
+// (2e-9 s at 1e7 s, times PWF0 of 1e-4 Hz: 2e-13 cycle) the sum of 1e3 - 1e4 cycles rounds at
+// 1e-12 cycle, three orders under the 1e-10 s bar
+PD double pw_phase_at(const double* B, double dt) {
+    return pval(B, 2 * PINT_PW_PH) +
+           dt * (pval(B, 2 * PINT_PW_F0) +
+                 dt * (0.5 * pval(B, 2 * PINT_PW_F1) + dt * ((1.0 / 6.0) * pval(B, 2 * PINT_PW_F2))));
+}
+PD dd pw_row_phase(const double* B, int npw, dd tdb, double delay, dd ph) {
+    for (int k = 0; k < npw; k++, B += 2 * PINT_PW_NPAR) {
+        double dt;
+        if (pw_dt(B, tdb, delay, dt)) ph = dd_add_d(ph, pw_phase_at(B, dt));  // (overlapping pieces both add)
+    }
+    return ph;
+}
+// the PINT_COL_PW columns of design-matrix row r (Mb, ld, runs, compact as in eval_spin_b):
+// -d_phase_d_F / F0 (:237-253), exactly 0 outside the piece's window.  A run lies within one
+// piece or crosses into the next.
+PD void pw_row_columns(const double* B0, dd tdb, double delay, double iF0, double* Mb, unsigned r, long ld,
+                       const ColRun* runs, int nrun, bool compact) {
+    for (int u = 0; u < nrun; u++) {
+        const ColRun R = runs[u];
+        if (R.kind != PINT_COL_PW) continue;
+        double* colp = Mb + (long)(compact ? R.dcol0 : R.col0) * ld;
+        for (int j = 0; j < R.cnt; j++, colp += ld) {
+            const int k = (R.idx0 + j) >> 2, which = (R.idx0 + j) & 3;
+            double dt;
+            const bool in = pw_dt(B0 + 2 * PINT_PW_NPAR * k, tdb, delay, dt);
+            const double d = which == 0 ? 1.0 : which == 1 ? dt : which == 2 ? 0.5 * dt * dt : (1.0 / 6.0) * dt * dt * dt;
+            colp[r] = in ? -d * iF0 : 0.0;
+        }
+    }
+}
+// Wave (wave.py:148-168): times = sum_k a_k sin(k b) + b_k cos(k b) seconds, k = 1 ... nwave,
+// b = WAVE_OM (tdb - WAVEEPOCH - delay / 86400 s) in radians (no 2 pi: WAVE_OM is an angular
+// frequency).  W: the component's block, the dd pairs of WAVEEPOCH and WAVE_OM, then the (a_k,
+// b_k) doubles.  The time difference is formed in dd and rounded once (1e-13 d at 1e3 d); b, of
+// order 10 rad, then carries 1e-15 rad in double, and at the 128th term 1e-13 rad: against the
+// bar of 1e-10 s on amplitudes up to a second, 1e-10 rad is what is needed.  sin(k b), cos(k b)
+// advance by rotation from one sincos: each step adds ~1 ulp, 128 steps 3e-14, so the
+// recurrence holds the bar by three orders and a sincos per term buys nothing.
+PD double wave_times(const double* W, int nwave, dd tdb, double delay) {
+    const dd dtd = dd_add_d(dd_sub(tdb, pdd(W, 0)), -delay * (1.0 / DAYSEC));
+    const double b = pval(W, 2) * dd_to_d(dtd);
+    double s1, c1;
+    sincos(b, &s1, &c1);
+    double s = s1, c = c1, t = 0.0;
+    const double* A = W + 4;
+    for (int k = 0; k < nwave; k++) {
+        t += A[2 * k] * s;
+        t += A[2 * k + 1] * c;
+        const double sn = s * c1 + c * s1;
+        c = c * c1 - s * s1;
+        s = sn;
+    }
+    return t;
+}
+// IFunc (ifunc.py:113-148): the interpolated offset in seconds at ts = tdb - delay / 86400 s, from
+// the control points (xh + xl MJD, non-decreasing; y s), n >= 1 (type 0: n >= 3; the setter
+// checks both).  idx = the number of points before ts (numpy's searchsorted, side left), by a
+// binary search with dd comparisons; rows sorted in time walk the same few cache lines within a
+// wave.  Type 2: linear between the points, y_0 up to x_0, y_{n-1} after x_{n-1}; the two
+// differences are formed in dd and rounded once, and the quotient in double carries 2e-16 of
+// an offset of at most seconds.  Type 0 as the reference runs it (:131-134), which is not its
+// comment: y_0 before x_0, y_{n-1} from x_1 (the second point) on, and y_{idx+1} between.
+PD double ifunc_times(const double* xh, const double* xl, const double* y, int n, int type, dd tdb, double delay) {
+    const dd ts = dd_add_d(tdb, -delay * (1.0 / DAYSEC));
+    int lo = 0, hi = n;
+    while (lo < hi) {  // (mid in 0 ... n - 1)
+        const int mid = (lo + hi) >> 1;
+        const double h = xh[mid];
+        if (h < ts.hi || (h == ts.hi && xl[mid] < ts.lo)) lo = mid + 1; else hi = mid;
+    }
+    if (type == 0) {
+        if (ts.hi < xh[0] || (ts.hi == xh[0] && ts.lo < xl[0])) return y[0];
+        if (!(ts.hi < xh[1] || (ts.hi == xh[1] && ts.lo < xl[1]))) return y[n - 1];
+        return y[lo + 1];  // (x_0 <= ts < x_1: lo is 0 or 1, and n >= 3)
+    }
+    if (lo == 0) return y[0];
+    if (lo == n) return y[n - 1];
+    const double dx1 = dd_to_d(dd_sub(ts, dd_make(xh[lo - 1], xl[lo - 1])));
+    const double dx2 = dd_to_d(dd_sub(dd_make(xh[lo], xl[lo]), ts));
+    return (y[lo] * dx1 + y[lo - 1] * dx2) / (dx1 + dx2);
+}
+
 // eval_toa's spindown phase, jumps and PhaseOffset, then the design-matrix row but for the
 // binary columns (written by eval_toa while the binary state is live)
 template <int BIN>

@@ -122,6 +122,11 @@ struct PsrDev {
     int o_fdj, nfdj, o_fdjdm, nfdjdm, fdj_log;
     const int32_t* fdj_index;
     const uint64_t *fdjmask, *fdjdmmask;
+    // PiecewiseSpindown / Wave / IFunc (pint_set_phase_terms): the pieces' block (PINT_PW_NPAR dd
+    // pairs per piece) and count; Wave's block (WAVEEPOCH and WAVE_OM pairs, then (a, b) doubles
+    // per term) and count; IFunc's type, count and control points (x as hi and lo, y)
+    int o_pw, npw, o_wave, nwave, sifunc, nifunc;
+    const double *ifx_hi, *ifx_lo, *ify;
 };
 
 struct InstDev {
@@ -1014,6 +1019,47 @@ __global__ __launch_bounds__(256) void k_glitch(const PsrDev* __restrict__ psrs,
     if (Mout && r < I.n)
         glitch_row_columns(S, P, tdb, dl, ic[blockIdx.x].iF0, Mout + I.moff, (unsigned)r, I.n, Pd.runs, Pd.nrun,
                            compact && Pd.dsplit);
+}
+
+// k_phase_terms: the PiecewiseSpindown, Wave and IFunc components (piecewise.py:181-253,
+// wave.py:148-168, ifunc.py:113-148) of the instances whose model has any of them
+// (pint_set_phase_terms), after k_wavex and k_fdjump (which move the delay) and beside k_glitch,
+// in k_glitch's form: every evaluation row's phase (TOAs and the TZR row) gains the three
+// components' phases at the row's total delay, and with Mout the PINT_COL_PW columns of the TOAs'
+// rows are written (the evaluation leaves them zero), in the full or the compact fit layout.
+// None of the three registers a derivative with respect to the delay, so no other column moves.
+// A batch with them runs its residual pass after this kernel, not fused into the evaluation.
+// One thread per row; grid (instances, row blocks of the longest instance); the pieces and the
+// Wave terms are read at block-uniform addresses, IFunc's points by a per-row binary search
+// (physics.hpp); no LDS, no atomics.  ~50 B/row plus 8 B per free piece column.
+__global__ __launch_bounds__(256) void k_phase_terms(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
+                                                     const double* __restrict__ tables,
+                                                     const InstConst* __restrict__ ic,
+                                                     const double* __restrict__ delay, double* __restrict__ ph_hi,
+                                                     double* __restrict__ ph_lo, double* __restrict__ Mout,
+                                                     int compact) {
+    const InstDev I = insts[blockIdx.x];
+    const PsrDev& Pd = psrs[I.psr];
+    const int npw = Pd.npw, nwave = Pd.nwave, nif = Pd.nifunc;
+    if (npw + nwave + nif <= 0) return;  // (block-uniform)
+    const int r = blockIdx.y * 256 + threadIdx.x;
+    if (r > I.n) return;
+    const double* P = tables + I.toff;
+    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
+    const double dl = delay[I.roff + r];
+    dd ph = dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]);
+    if (npw > 0) ph = pw_row_phase(P + Pd.o_pw, npw, tdb, dl, ph);
+    // Wave and IFunc: seconds, summed and turned into cycles by F0 (a few cycles at most: the
+    // product in double rounds at 1e-16 cycle)
+    double times = 0.0;
+    if (nwave > 0) times += wave_times(P + Pd.o_wave, nwave, tdb, dl);
+    if (nif > 0) times += ifunc_times(Pd.ifx_hi, Pd.ifx_lo, Pd.ify, nif, Pd.sifunc, tdb, dl);
+    if (nwave + nif > 0) ph = dd_add_d(ph, pval(P, Pd.spec->o_F) * times);
+    ph_hi[I.roff + r] = ph.hi;
+    ph_lo[I.roff + r] = ph.lo;
+    if (Mout && npw > 0 && r < I.n)
+        pw_row_columns(P + Pd.o_pw, tdb, dl, ic[blockIdx.x].iF0, Mout + I.moff, (unsigned)r, I.n, Pd.runs, Pd.nrun,
+                       compact && Pd.dsplit);
 }
 
 // Spin-only grids (pint_set_grid's variables all spin frequencies, isolated model, no
@@ -6006,6 +6052,7 @@ struct pint_ctx {
     bool any_wavex = false;       // ... has WaveX or DMWaveX: k_wavex follows the evaluation (before k_glitch)
     bool any_chrom = false;       // ... has ChromaticCM / CMWaveX: k_wavex<true> instead (any_wavex is set too)
     bool any_fdjump = false;      // ... has FDJump / FDJumpDM: k_fdjump follows k_wavex (before k_glitch)
+    bool any_phase_terms = false; // ... has PiecewiseSpindown / Wave / IFunc: k_phase_terms follows k_fdjump
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
@@ -6953,6 +7000,7 @@ int pint_add_pulsar(pint_ctx* ctx, const pint_toas_t* t, const pint_spec_t* spec
     d.o_wx = d.o_dmwx = -1;  // (pint_set_wavex)
     d.o_cm = d.o_cmwx = -1;  // (pint_set_chromatic)
     d.o_fdj = d.o_fdjdm = -1;  // (pint_set_fdjump)
+    d.o_pw = d.o_wave = -1;    // (pint_set_phase_terms)
     int rc = 0;
     rc |= stg(t->tdb_hi, n + 1, d.tdb_hi);
     rc |= stg(t->tdb_lo, n + 1, d.tdb_lo);
@@ -7188,6 +7236,63 @@ int pint_set_fdjump(pint_ctx* ctx, int psr, int o_fdj, int nfdj, const int32_t* 
     d.o_fdjdm = nfdjdm > 0 ? o_fdjdm : -1;
     d.nfdjdm = nfdjdm;
     d.fdj_log = use_log ? 1 : 0;
+    ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
+    return PINT_OK;
+}
+
+int pint_set_phase_terms(pint_ctx* ctx, int psr, int o_pw, int npw, int o_wave, int nwave, int sifunc, int nifunc,
+                         const double* ifunc_x_hi, const double* ifunc_x_lo, const double* ifunc_y) {
+    if (!ctx) return PINT_E_INVALID;
+    if (psr < 0 || psr >= (int)ctx->psrs.size()) { ctx->err = "pint_set_phase_terms: bad pulsar id"; return PINT_E_INVALID; }
+    PsrHost& ph = ctx->psrs[psr];
+    const long ts = (long)ph.spec.tstride;
+    // the pieces: PINT_PW_NPAR dd pairs each; Wave: two dd pairs, then a pair of doubles per term;
+    // both inside the table.  IFunc: its three arrays, the type 0 or 2 (type 0 reads y_2), x
+    // non-decreasing as dd
+    const bool bad_pw = npw < 0 || npw > PINT_MAX_PW || (npw > 0 && (o_pw < 0 || (long)o_pw + 2L * PINT_PW_NPAR * npw > ts));
+    const bool bad_wave = nwave < 0 || nwave > PINT_MAX_WAVE || (nwave > 0 && (o_wave < 0 || (long)o_wave + 4L + 2L * nwave > ts));
+    bool bad_if = nifunc < 0 || nifunc > PINT_MAX_IFUNC;
+    if (!bad_if && nifunc > 0) {
+        bad_if = !ifunc_x_hi || !ifunc_x_lo || !ifunc_y || (sifunc != 0 && sifunc != 2) || (sifunc == 0 && nifunc < 3);
+        for (int k = 1; !bad_if && k < nifunc; k++)
+            bad_if = ifunc_x_hi[k] < ifunc_x_hi[k - 1] ||
+                     (ifunc_x_hi[k] == ifunc_x_hi[k - 1] && ifunc_x_lo[k] < ifunc_x_lo[k - 1]);
+        for (int k = 0; !bad_if && k < nifunc; k++)
+            bad_if = !std::isfinite(ifunc_x_hi[k]) || !std::isfinite(ifunc_x_lo[k]);
+    }
+    if (bad_pw || bad_wave || bad_if) {
+        ctx->err = "bad PiecewiseSpindown / Wave block or count, or IFunc count, type, pointer or point order "
+                   "(PINT_MAX_PW, PINT_MAX_WAVE, PINT_MAX_IFUNC; SIFUNC 0 or 2, SIFUNC 0 with >= 3 points)";
+        return PINT_E_INVALID;
+    }
+    if (ph.dev.wb) {  // (no wideband form of the three has been checked against the reference)
+        ctx->err = "wideband DM data with PiecewiseSpindown / Wave / IFunc is not supported";
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    // device copies of the library's own, kept with the pulsar's other allocations (a repeated
+    // call leaves the earlier copies to the pulsar's release)
+    PsrDev& d = ph.dev;
+    const double *xh = nullptr, *xl = nullptr, *yy = nullptr;
+    if (nifunc > 0) {
+        int rc = 0;
+        rc |= upload(ctx, ph, ifunc_x_hi, (size_t)nifunc, xh);
+        rc |= upload(ctx, ph, ifunc_x_lo, (size_t)nifunc, xl);
+        rc |= upload(ctx, ph, ifunc_y, (size_t)nifunc, yy);
+        if (rc) {  // (the pulsar keeps what it had)
+            ctx->err = "pint_set_phase_terms: device allocation or copy failed";
+            return PINT_E_HIP;
+        }
+    }
+    d.ifx_hi = xh;
+    d.ifx_lo = xl;
+    d.ify = yy;
+    d.nifunc = nifunc;
+    d.sifunc = nifunc > 0 ? sifunc : 0;
+    d.o_pw = npw > 0 ? o_pw : -1;
+    d.npw = npw;
+    d.o_wave = nwave > 0 ? o_wave : -1;
+    d.nwave = nwave;
     ctx->psrs_dirty = true;  // (the device descriptors are rebuilt at pint_set_instances)
     return PINT_OK;
 }
@@ -7429,8 +7534,14 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
         const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
         ctx->any_fdjump = ctx->any_fdjump || d.nfdj + d.nfdjdm > 0;
     }
+    // (nor with PiecewiseSpindown / Wave / IFunc: k_phase_terms adds their phase after the evaluation)
+    ctx->any_phase_terms = false;
+    for (int k = 0; k < ninst; k++) {
+        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
+        ctx->any_phase_terms = ctx->any_phase_terms || d.npw + d.nwave + d.nifunc > 0;
+    }
     ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch && !ctx->any_wavex &&
-               !ctx->any_fdjump;
+               !ctx->any_fdjump && !ctx->any_phase_terms;
     long ebn = 0;
     // N-split for the Gram so the launch fills the 256 CUs
     // choose the split count that minimises (workgroup rounds) / nsplit, i.e. the k_gram
@@ -8222,6 +8333,12 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                            want_M == 2 ? 1 : 0);
         HIPCHK(hipGetLastError());
     }
+    if (ctx->any_phase_terms) {  // PiecewiseSpindown / Wave / IFunc: their phases at the final delay, the piece columns
+        hipLaunchKernelGGL(k_phase_terms, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream,
+                           ctx->d_psrs, ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo,
+                           want_M ? ctx->d_M : nullptr, want_M == 2 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
     record(ctx, want_M ? 3 : 1);
     record(ctx, 4);
     if (ctx->nrblk > 0) {
@@ -8291,6 +8408,10 @@ int pint_set_wideband(pint_ctx* ctx, int psr, const double* pp_dm, const double*
     }
     if (ph.dev.nfdj + ph.dev.nfdjdm > 0) {  // (FDJumpDM adds to the modelled DM: the DM rows do not form it)
         ctx->err = "wideband DM data with FDJump / FDJumpDM is not supported";
+        return PINT_E_INVALID;
+    }
+    if (ph.dev.npw + ph.dev.nwave + ph.dev.nifunc > 0) {  // (no wideband fixture with them exists)
+        ctx->err = "wideband DM data with PiecewiseSpindown / Wave / IFunc is not supported";
         return PINT_E_INVALID;
     }
     if (ph.dev.ncm + ph.dev.ncmwx > 0) {  // (no wideband chromatic fixture exists)

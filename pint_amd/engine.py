@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib as L
 from .noise import red_noise_freqs_weights, scaled_sigma_us
 from .parameter import LD
-from .timing_model import BIN_IDS, GLITCH_PROPS, OBLIQUITY, TimingModel
+from .timing_model import BIN_IDS, GLITCH_PROPS, OBLIQUITY, PW_FITTABLE, PW_PROPS, TimingModel
 
 UNITS = {  # design-matrix column units as the reference prints them (per par unit / F0)
     "RAJ": "1 / (hourangle Hz)", "DECJ": "1 / (deg Hz)", "ELONG": "1 / (deg Hz)", "ELAT": "1 / (deg Hz)",
@@ -59,6 +59,11 @@ class PulsarLayout:
     # FDJump / FDJumpDM (pint_set_fdjump): (o_fdj, nfdj, fd_index int32[nfdj], use_log, mask uint64[n + 1],
     # o_fdjdm, nfdjdm, dmmask uint64[n + 1]), None for a model with neither
     fdjump: Optional[tuple] = None
+    # PiecewiseSpindown / Wave / IFunc (pint_set_phase_terms): (o_pw, npw, o_wave, nwave, sifunc, nifunc,
+    # x_hi float64[nifunc], x_lo float64[nifunc], y float64[nifunc]), None for a model with none of them
+    phase_terms: Optional[tuple] = None
+    # Wave's (a, b) pairs in the table: (slot, parameter name), two plain doubles at the slot
+    pairs: list = field(default_factory=list)
 
 
 def _track_mode(model, toas, track_mode):
@@ -243,6 +248,50 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         use_log = 1 if ("FDJUMPLOG" not in model or model.FDJUMPLOG.value) else 0
         fdj_desc = (starts[0], len(fdjs), np.array([model.get_fd_index(n) for n in fdjs] or [0], dtype=np.int32),
                     use_log, masks[0], starts[1], len(fdjdms), masks[1])
+    # PiecewiseSpindown: one block of 7 dd pairs per piece, ascending index, PW_PROPS order; Wave:
+    # the dd pairs of WAVEEPOCH and WAVE_OM, then one pair of doubles (a_k, b_k) per term; IFunc:
+    # the control points as arrays of their own (never fitted or gridded: they do not belong in
+    # every instance's table).  Beside the spec (pint_set_phase_terms)
+    pt_desc, pairs = None, []
+    pieces = model.pw_indices()
+    waves = model.wave_terms()
+    ifuncs = model.ifunc_terms()
+    if pieces or waves or ifuncs:
+        for cnt, cap, what in ((len(pieces), L.MAX_PW, "PiecewiseSpindown pieces (PINT_MAX_PW)"),
+                               (len(waves), L.MAX_WAVE, "Wave terms (PINT_MAX_WAVE)"),
+                               (len(ifuncs), L.MAX_IFUNC, "IFunc control points (PINT_MAX_IFUNC)")):
+            if cnt > cap:
+                raise NotImplementedError(f"more than {cap} {what}")
+        o_pw = pos if pieces else -1
+        for k, idx in enumerate(pieces):
+            for pre in PW_PROPS:
+                place(f"{pre}{idx}")
+            for w, pre in enumerate(PW_FITTABLE):
+                wx_cols[f"{pre}{idx}"] = (L.COL_PW, 4 * k + w)
+        o_wave = -1
+        if waves:
+            o_wave = place("WAVEEPOCH")
+            place("WAVE_OM")
+            for n in waves:
+                pairs.append((pos, n))
+                pos += 2
+        sifunc = 0
+        xh = xl = yy = np.zeros(1)
+        if ifuncs:
+            # IFunc.ifunc_phase (ifunc.py:124-146): SIFUNC 0 and 2 only; SIFUNC 0 reads the third point
+            sifunc = int(model.SIFUNC.value)
+            if sifunc not in (0, 2):
+                raise ValueError(f"Interpolation type {sifunc} not supported.")
+            if sifunc == 0 and len(ifuncs) < 3:
+                raise ValueError("SIFUNC 0 needs at least three IFUNC points (the reference indexes the third)")
+            x = np.array([model[n].value[0] for n in ifuncs], dtype=np.longdouble)
+            if np.any(np.diff(x) < 0):
+                raise ValueError("the IFUNC control points must ascend in MJD")
+            xh = x.astype(np.float64)
+            xl = (x - xh.astype(np.longdouble)).astype(np.float64)
+            yy = np.array([float(model[n].value[1]) for n in ifuncs], dtype=np.float64)
+        pt_desc = (o_pw, len(pieces), o_wave, len(waves), sifunc, len(ifuncs), np.ascontiguousarray(xh),
+                   np.ascontiguousarray(xl), np.ascontiguousarray(yy))
     spec.binary = {None: L.BIN_NONE, "ELL1": L.BIN_ELL1, "DD": L.BIN_DD, "ELL1H": L.BIN_ELL1H, "BT": L.BIN_BT,
                    "DDK": L.BIN_DDK, "DDS": L.BIN_DDS, "DDH": L.BIN_DDH, "ELL1k": L.BIN_ELL1K}[model.binary]
     spec.k96 = 0 if (model.binary == "DDK" and "K96" in model and model.K96.value is False) else 1
@@ -374,6 +423,8 @@ def build_layout(model: TimingModel, toas, track_mode=None, subtract_mean=True, 
         lay.wavex = tuple(wx_desc)
     lay.chromatic = chrom_desc
     lay.fdjump = fdj_desc
+    lay.phase_terms = pt_desc
+    lay.pairs = pairs
     if ep_lists:
         lay.nep = len(ep_lists)
         lay.ep_ptr = np.concatenate([[0], np.cumsum([len(e) for e in ep_lists])]).astype(np.int32)
@@ -398,6 +449,8 @@ def pack_table(lay: PulsarLayout, model: Optional[TimingModel] = None) -> np.nda
     hi = v.astype(np.float64)
     tab[o] = hi
     tab[o + 1] = (v - hi.astype(np.longdouble)).astype(np.float64)
+    for slot, n in lay.pairs:  # (Wave's amplitudes: two plain doubles)
+        tab[slot], tab[slot + 1] = float(p[n].value[0]), float(p[n].value[1])
     return tab
 
 
@@ -728,6 +781,10 @@ class Session:
             o_fdj, nfdj, fdidx, use_log, mask, o_dm, ndm, dmmask = lay.fdjump
             self._check(self.L.pint_set_fdjump(self.ctx, pid, o_fdj, nfdj, L.ptr(fdidx, C.c_int32), use_log,
                                                L.ptr(mask, C.c_uint64), o_dm, ndm, L.ptr(dmmask, C.c_uint64)))
+        if lay.phase_terms is not None:
+            o_pw, npw, o_wave, nwave, sifunc, nif, xh, xl, yy = lay.phase_terms
+            self._check(self.L.pint_set_phase_terms(self.ctx, pid, o_pw, npw, o_wave, nwave, sifunc, nif,
+                                                    L.ptr(xh), L.ptr(xl), L.ptr(yy)))
         self.layouts.append(lay)
         return lay
 

@@ -563,7 +563,9 @@ class Fitter:
         # the wideband DM rows (k_dm_resid, k_wb_gram) do not form: refuse, do not fit a wrong DM
         # (nor is there a wideband form of the chromatic components' share of the DM rows)
         # (FDJumpDM adds -FDJUMPDM to the modelled DM of its TOAs, dispersion_model.py:859-871, like DMWaveX)
-        for comp in ("WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM"):
+        # (nor has a wideband fit with PiecewiseSpindown, Wave or IFunc been checked against the reference)
+        for comp in ("WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM", "PiecewiseSpindown", "Wave",
+                     "IFunc"):
             if comp in getattr(model, "components", {}) and hasattr(toas, "is_wideband") and toas.is_wideband():
                 raise NotImplementedError(f"wideband TOAs with a {comp} component are outside the supported "
                                           "hot path")

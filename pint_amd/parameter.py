@@ -63,7 +63,7 @@ class Param:
     """One timing-model parameter (subset of the reference Parameter API)."""
 
     name: str
-    kind: str = "float"  # float | mjd | hourangle | degangle | str | bool | int | mask
+    kind: str = "float"  # float | mjd | hourangle | degangle | str | bool | int | mask | pair
     units: str = ""
     long_double: bool = False
     value: object = None
@@ -99,6 +99,12 @@ class Param:
             if self.scale is not None and abs(float(v)) > abs(self.scale[1]):
                 v = v * (LD(self.scale[0]) if self.long_double else self.scale[0])
             self.value = v
+
+    def set_pair_from_strings(self, a: str, b: str):
+        """A pair parameter's two values (parameter.py:2264-2289 pairParameter: ``NAME v1 v2``, a
+        third number on the line is ignored; never free, and no uncertainty)."""
+        conv = data2longdouble if self.long_double else fortran_float
+        self.value = (conv(a), conv(b))
 
     def set_uncertainty_from_string(self, s: str):
         try:
@@ -217,6 +223,11 @@ _DEFS = {
     "CMWXEPOCH": ("CMWaveX", "mjd", "d", True, None),
     # FDJump's switch (fdjump.py:69-75): log(f / GHz) (Y) or f / GHz (N) as the polynomial's argument
     "FDJUMPLOG": ("FDJump", "bool", "", False, None),
+    # Wave (wave.py:30-58): the epoch and the base angular frequency; IFunc's interpolation type
+    # (ifunc.py:59-66, a floatParameter)
+    "WAVEEPOCH": ("Wave", "mjd", "d", True, None),
+    "WAVE_OM": ("Wave", "float", "1 / d", False, None),
+    "SIFUNC": ("IFunc", "float", "", False, None),
     # binaries (pulsar_binary.py, binary_ell1.py, binary_dd.py)
     "PB": ("Binary", "float", "d", True, None),
     "PBDOT": ("Binary", "float", "", False, (1e-12, 1e-7)),
@@ -291,7 +302,21 @@ _PREFIX = {  # prefix params: regex -> (component, units template, long_double)
     r"^CMWXFREQ_(\d{4})$": ("CMWaveX", "1 / d", False),
     r"^CMWXSIN_(\d{4})$": ("CMWaveX", "pc / (cm3 MHz2)", False),
     r"^CMWXCOS_(\d{4})$": ("CMWaveX", "pc / (cm3 MHz2)", False),
+    # Wave's terms (sine and cosine amplitude, s) and IFunc's control points (MJD, s): pair
+    # parameters, longdouble (wave.py:48-58, ifunc.py:67-77)
+    r"^WAVE(\d+)$": ("Wave", "s", True),
+    r"^IFUNC(\d+)$": ("IFunc", "s", True),
+    # PiecewiseSpindown (piecewise.py:54-123): three epochs (MJD) and four float64 spin terms per piece
+    r"^PWSTART_(\d+)$": ("PiecewiseSpindown", "d", True),
+    r"^PWSTOP_(\d+)$": ("PiecewiseSpindown", "d", True),
+    r"^PWEP_(\d+)$": ("PiecewiseSpindown", "d", True),
+    r"^PWPH_(\d+)$": ("PiecewiseSpindown", "", False),
+    r"^PWF0_(\d+)$": ("PiecewiseSpindown", "Hz", False),
+    r"^PWF1_(\d+)$": ("PiecewiseSpindown", "Hz / s", False),
+    r"^PWF2_(\d+)$": ("PiecewiseSpindown", "Hz / s2", False),
 }
+PAIR_NAME = re.compile(r"^(WAVE|IFUNC)\d+$")
+MJD_PREFIXES = ("DMXR", "GLEP_", "PWSTART_", "PWSTOP_", "PWEP_")
 
 MASK_PARAMS = {"JUMP": ("PhaseJump", "s"), "EFAC": ("ScaleToaError", ""),
                "EQUAD": ("ScaleToaError", "us"), "TNEQ": ("ScaleToaError", "log10(s)"),
@@ -330,7 +355,7 @@ def make_param(name: str) -> Optional[Param]:
         m = re.match(rx, name)
         if m:
             idx = int(m.group(1))
-            kind = "mjd" if name.startswith(("DMXR", "GLEP_")) else "float"
+            kind = "mjd" if name.startswith(MJD_PREFIXES) else ("pair" if PAIR_NAME.match(name) else "float")
             u = units.replace("{n+1}", str(idx + 1)).replace("{n}", str(idx))
             if name == "F0":
                 u = "Hz"

@@ -211,6 +211,9 @@ def parfile_line(p: Param) -> str:
     if getattr(p, "implicit", False) and p.frozen and p.value == 0:
         return ""  # a default the reference leaves unset (None): not written
     name = _display_name(p)
+    if p.kind == "pair":  # pairParameter.as_parfile_line (parameter.py:2291-2300): no fit flag, no uncertainty
+        conv = (lambda x: str(LD(x))) if p.long_double else (lambda x: str(float(x)))
+        return "%-15s %25s %25s\n" % (name, conv(p.value[0]), conv(p.value[1]))
     if p.kind == "mask":
         line = "%-15s %s " % (name, p.key)
         kl = p.key.lower()
@@ -256,7 +259,7 @@ _ORDER = {
     "PLDMNoise": ["TNDMAMP", "TNDMGAM", "TNDMC"],
 }
 MIDDLE = ["TroposphereDelay", "SolarSystemShapiro", "SolarWindDispersion", "DispersionDM", "DispersionDMX",
-          "Binary", "FD", "WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM", "AbsPhase", "Glitch", "PhaseOffset", "PhaseJump", "EcorrNoise",
+          "Binary", "FD", "WaveX", "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM", "AbsPhase", "Wave", "Glitch", "PiecewiseSpindown", "IFunc", "PhaseOffset", "PhaseJump", "EcorrNoise",
           "ScaleToaError", "PLRedNoise", "PLDMNoise"]
 
 
@@ -291,6 +294,13 @@ def _component_params(model, comp: str) -> List[str]:
     if comp == "Glitch":  # Glitch.print_par (glitch.py:185-191): per glitch, in glitch_prop's order
         from .timing_model import GLITCH_PROPS
         return [f"{pre}{i}" for i in model.glitch_indices() for pre in GLITCH_PROPS if f"{pre}{i}" in P]
+    if comp == "PiecewiseSpindown":  # print_par (piecewise.py:173-179): per piece, in pwsol_prop's order
+        from .timing_model import PW_PROPS
+        return [f"{pre}{i}" for i in model.pw_indices() for pre in PW_PROPS if f"{pre}{i}" in P]
+    if comp == "Wave":  # print_par (wave.py:89-99): the epoch, the frequency, WAVE1 ... WAVEn
+        return [n for n in ("WAVEEPOCH", "WAVE_OM") if n in names] + _by_index(names, "WAVE")
+    if comp == "IFunc":  # print_par (ifunc.py:104-111): SIFUNC, IFUNC1 ... IFUNCn
+        return [n for n in ("SIFUNC",) if n in names] + _by_index(names, "IFUNC")
     if comp in _ORDER:
         return [n for n in _ORDER[comp] if n in names] + [n for n in names if n not in _ORDER[comp]]
     return names

@@ -23,7 +23,7 @@ from .parameter import LD, Param
 DELAY_ORDER = ["AstrometryEquatorial", "AstrometryEcliptic", "TroposphereDelay", "SolarSystemShapiro",
                "SolarWindDispersion", "DispersionDM", "DispersionDMX", "BinaryELL1", "BinaryDD", "FD", "WaveX",
                "DMWaveX", "ChromaticCM", "CMWaveX", "FDJump", "FDJumpDM"]
-PHASE_ORDER = ["AbsPhase", "Spindown", "Glitch", "PhaseOffset", "PhaseJump"]
+PHASE_ORDER = ["AbsPhase", "Spindown", "Wave", "Glitch", "PiecewiseSpindown", "IFunc", "PhaseOffset", "PhaseJump"]
 NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
 
 # Glitch (glitch.py): the parameters of one glitch in the order setup / print_par walk them
@@ -31,6 +31,17 @@ NOISE = ["ScaleToaError", "EcorrNoise", "PLRedNoise", "PLDMNoise"]
 # PINT_GL_*; and the order the component declares its index-1 parameters in (:56-124)
 GLITCH_PROPS = ("GLEP_", "GLPH_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_")
 GLITCH_DECLARED = ("GLPH_", "GLEP_", "GLF0_", "GLF1_", "GLF2_", "GLF0D_", "GLTD_")
+
+# PiecewiseSpindown (piecewise.py): the parameters of one piece in the order setup / print_par walk
+# them (pwsol_prop, :130-138), which is also the order of a piece's 7 table slots and of PINT_PW_*;
+# and the order the component declares its index-1 parameters in (:54-123).  Wave (category wave)
+# is in the reference's DEFAULT_ORDER, after phase_jump; piecewise and ifunc are not, like glitch,
+# so their place among the phase components changes with the interpreter's hash seed.  Here the
+# order is always Spindown, Wave, Glitch, PiecewiseSpindown, IFunc (the order of the run the
+# pw_wls / wave_wls fixtures were captured in).
+PW_PROPS = ("PWEP_", "PWSTART_", "PWSTOP_", "PWPH_", "PWF0_", "PWF1_", "PWF2_")
+PW_DECLARED = ("PWSTART_", "PWSTOP_", "PWEP_", "PWPH_", "PWF0_", "PWF1_", "PWF2_")
+PW_FITTABLE = ("PWPH_", "PWF0_", "PWF1_", "PWF2_")
 
 # WaveX / DMWaveX (wavex.py, dmwavex.py): component -> parameter-name stem.  wavex is the last
 # category of the reference's DEFAULT_ORDER and dmwavex is not in it (it sorts after everything,
@@ -77,6 +88,10 @@ class MissingParameter(ValueError):
 
 class TimingModelError(ValueError):
     """timing_model.py TimingModelError (an invalid model structure)."""
+
+
+class UnknownParameter(TimingModelError):
+    """timing_model.py UnknownParameter (a name no component of the model declares)."""
 
 
 class UnknownBinaryModel(TimingModelError):
@@ -168,8 +183,12 @@ class TimingModel:
                 return 1
             if c == "Spindown":
                 return 2
-            if c == "Glitch":  # a phase component: after Spindown, before the delay components
+            if c == "Wave":  # the phase components: after Spindown, before the delay components
+                return 2.5
+            if c == "Glitch":
                 return 3
+            if c in ("PiecewiseSpindown", "IFunc"):
+                return 3.2 if c == "PiecewiseSpindown" else 3.3
             return rest.get(c, big)
         ranks = {c: rank(c) for c in {p.component for p in self._params.values()}}
         if "Glitch" not in ranks:
@@ -372,6 +391,60 @@ class TimingModel:
                     p.value = 0.0
                     self.add_param(p)
 
+    # -- PiecewiseSpindown, Wave, IFunc (piecewise.py, wave.py, ifunc.py) -------------------------
+    def pw_indices(self) -> List[int]:
+        """The piece indices that appear in any PW*_n parameter, ascending (piecewise.py:139-144)."""
+        return self._names_of("pw", lambda: sorted({p.index for p in self._params.values()
+                                                    if p.component == "PiecewiseSpindown"}))
+
+    def wave_terms(self) -> List[str]:
+        """WAVE1, WAVE2, ... in ascending index (the terms that have a value)."""
+        return [n for n in self.prefix_list(r"^WAVE(\d+)$") if self._params[n].value is not None]
+
+    def ifunc_terms(self) -> List[str]:
+        """IFUNC1, IFUNC2, ... in ascending index (the control points that have a value)."""
+        return [n for n in self.prefix_list(r"^IFUNC(\d+)$") if self._params[n].value is not None]
+
+    def validate_phase_terms(self):
+        """PiecewiseSpindown.setup / validate (piecewise.py:128-171), Wave.validate (wave.py:66-87)
+        and IFunc.validate (ifunc.py:85-102)."""
+        pieces = self.pw_indices()
+        for idx in pieces:  # (setup: register_deriv_funcs on a parameter the piece does not have)
+            for pre in PW_FITTABLE:
+                if f"{pre}{idx}" not in self._params:
+                    raise UnknownParameter(f"Unknown parameter name or alias {pre}{idx}")
+        for idx in pieces:
+            # (the reference's index-1 epochs always exist, unset, and fail at the first evaluation;
+            # here an unset epoch is as missing as an absent one)
+            for pre, what in (("PWEP_", "Epoch"), ("PWSTART_", "starting epoch"), ("PWSTOP_", "end epoch")):
+                p = self._params.get(f"{pre}{idx}")
+                if p is None or p.value is None:
+                    raise MissingParameter(f"PiecewiseSpindown.{pre}{idx} Piecewise solution {what} is needed "
+                                           f"for Piece {idx}.")
+        if "Wave" in self.components:
+            if self.WAVEEPOCH.value is None:
+                if "PEPOCH" not in self._params or self.PEPOCH.value is None:
+                    raise MissingParameter("Wave.WAVEEPOCH WAVEEPOCH or PEPOCH are required if WAVE_OM is set.")
+                self.WAVEEPOCH.value = LD(self.PEPOCH.value)
+            terms = [self._params[n].index for n in self.wave_terms()]
+            for k in range(1, max(terms, default=0) + 1):
+                if k not in terms:
+                    raise MissingParameter(f"Wave.WAVE{k}")
+            if terms and self.WAVE_OM.value is None:
+                # (the reference loads such a model and fails when the phase is first evaluated)
+                raise MissingParameter("Wave.WAVE_OM WAVE_OM is required if WAVE entries are present.")
+        if "IFunc" in self.components:
+            if self.SIFUNC.value is None:
+                raise MissingParameter("IFunc.SIFUNC SIFUNC is required if IFUNC entries are present.")
+            for i, n in enumerate(self.ifunc_terms()):
+                if self._params[n].index != i + 1:
+                    raise MissingParameter(f"IFunc.IFUNC{i + 1}")
+        if sum(c in self.components for c in ("Wave", "WaveX", "PLRedNoise", "IFunc")) > 1:
+            # (TimingModel.validate, timing_model.py: logged, not raised)
+            import logging
+            logging.getLogger("pint_amd").warning("Wave, WaveX, and PLRedNoise cannot be used together. They are "
+                                                  "ways of modelling the same effect.")
+
     # -- WaveX / DMWaveX (wavex.py:63-289, dmwavex.py) ------------------------------------------
     def _wavex_map(self, comp: str, part: str) -> Dict[int, str]:
         """get_prefix_mapping_component(f"{stem}{part}_"): {index: name} in parameter order."""
@@ -518,6 +591,7 @@ class TimingModel:
             if f0d is not None and f0d.value and not (td is not None and td.value):
                 raise MissingParameter(f"Glitch GLTD_{idx}: None zero GLF0D_{idx} parameter needs a none zero "
                                        f"GLTD_{idx} parameter")
+        self.validate_phase_terms()
         for comp in WAVEX_STEMS:
             self.validate_wavex(comp)
         if "ChromaticCM" in self.components:  # ChromaticCM.validate (chromatic_model.py:183-199)
@@ -735,6 +809,15 @@ def get_model(parfile) -> TimingModel:
     if any(n == "DM" or re.match(r"^DM\d+$", n) for n in names):
         defaults += [("DM", LD(0)), ("DMEPOCH", None)]
     wavex_rx = re.compile(r"^(DM|CM)?WX(EPOCH|(FREQ|SIN|COS)_\d+)$")
+    # PiecewiseSpindown, Wave and IFunc as constructed (piecewise.py:54-123: the index-1 piece with
+    # its epochs unset and its spin terms 0; wave.py:30-58; ifunc.py:59-77), where the phase
+    # components go: after Spindown
+    if any(re.match(r"^WAVE(EPOCH|_OM|\d+)$", n) for n in names):
+        defaults += [("WAVEEPOCH", None), ("WAVE_OM", None)]
+    if any(re.match(r"^PW(START|STOP|EP|PH|F0|F1|F2)_\d+$", n) for n in names):
+        defaults += [(f"{pre}1", None if pre in PW_DECLARED[:3] else 0.0) for pre in PW_DECLARED]
+    if any(re.match(r"^(SIFUNC|IFUNC\d+)$", n) for n in names):
+        defaults += [("SIFUNC", None)]
     if binary in ("ELL1", "ELL1H"):
         defaults += [(n, 0.0) for n in ELL1_PARAMS if not (binary == "ELL1H" and n in ("M2", "SINI"))]
         defaults += [("TASC", None)]
@@ -832,6 +915,10 @@ def get_model(parfile) -> TimingModel:
         if raw != name:
             p.alias = raw
         if not l.fields:
+            continue
+        if p.kind == "pair":  # (pairParameter.from_parfile_line: two values, whatever follows is ignored)
+            if len(l.fields) > 1:
+                p.set_pair_from_strings(l.fields[0], l.fields[1])
             continue
         p.set_from_string(l.fields[0])
         # TimingModel.validate (timing_model.py:405-413): the only values PINT supports

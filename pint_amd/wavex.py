@@ -6,8 +6,9 @@ The components themselves live in ``TimingModel`` (``add_wavex_component(s)``,
 ``remove_wavex_component``, ``get_wavex_indices``); their delays and design-matrix columns are
 the device kernel ``k_wavex``.  Frequencies are in 1 / d, WaveX amplitudes in s, DMWaveX
 amplitudes in pc / cm3, CMWaveX amplitudes in pc / cm3 / MHz2 (``cmwavex_setup``,
-``utils.py:1645-1736``; ``get_wavex_freqs`` / ``get_wavex_amps`` are WaveX's alone, as in the reference).  Not provided: ``find_optimal_nharms``, ``plrednoise_from_wavex``,
-``pldmnoise_from_dmwavex`` and the Wave <-> WaveX translations.
+``utils.py:1645-1736``; ``get_wavex_freqs`` / ``get_wavex_amps`` are WaveX's alone, as in the reference), and the Wave
+<-> WaveX translations (``utils.py:1794``, ``:1957``; host-only).  Not provided:
+``find_optimal_nharms``, ``plrednoise_from_wavex`` and ``pldmnoise_from_dmwavex``.
 """
 from __future__ import annotations
 
@@ -17,7 +18,8 @@ import numpy as np
 
 from .timing_model import WAVEX_STEMS
 
-__all__ = ["wavex_setup", "dmwavex_setup", "cmwavex_setup", "get_wavex_freqs", "get_wavex_amps"]
+__all__ = ["wavex_setup", "dmwavex_setup", "cmwavex_setup", "get_wavex_freqs", "get_wavex_amps",
+           "translate_wave_to_wavex", "translate_wavex_to_wave"]
 
 
 def _setup(model, comp, T_span, freqs, n_freqs, freeze_params):
@@ -64,6 +66,63 @@ def cmwavex_setup(model, T_span, freqs=None, n_freqs=None, freeze_params=False):
     """wavex_setup for CMWaveX (``utils.py:1645-1736``); amplitudes in pc / cm3 / MHz2.  The model
     needs a ChromaticCM component (CM, TNCHROMIDX) before it validates or evaluates."""
     return _setup(model, "CMWaveX", T_span, freqs, n_freqs, freeze_params)
+
+
+def _drop_component(model, comp):
+    for n in [n for n, p in model._params.items() if p.component == comp]:
+        model.remove_param(n)
+    model.components.pop(comp, None)
+
+
+def translate_wave_to_wavex(model):
+    """utils.py:1794-1838: a copy of the model with its Wave component replaced by a WaveX
+    component: WXEPOCH = WAVEEPOCH, WXFREQ_k = k WAVE_OM / (2 pi) for WAVEk, k = 1 ... n, and
+    WXSIN_k / WXCOS_k = -a_k / -b_k (a Wave term is a phase, a WaveX term a delay).  As in the
+    reference the first harmonic keeps the constructor's free amplitudes and the others are
+    frozen."""
+    from . import parameter as P
+    new = model.copy()
+    terms = [model[n] for n in model.wave_terms()]
+    om, epoch = model.WAVE_OM.value, model.WAVEEPOCH.value
+    _drop_component(new, "Wave")
+    new._ensure_wavex("WaveX")
+    new.WXEPOCH.value = P.LD(epoch)
+    for k, t in enumerate(terms):
+        a, b = t.value
+        f = (om * (k + 1)) / (2.0 * np.pi)
+        if k == 0:
+            new.WXFREQ_0001.value, new.WXSIN_0001.value, new.WXCOS_0001.value = float(f), float(-a), float(-b)
+        else:
+            new.add_wavex_component(f, wxsin=float(-a), wxcos=float(-b))
+    return new
+
+
+def translate_wavex_to_wave(model):
+    """utils.py:1957-1999: a copy of the model with its WaveX component replaced by a Wave
+    component.  Every harmonic must give the same WAVE_OM = 2 pi WXFREQ_k / k (to 1e-3 / d, the
+    reference's allclose); their mean becomes WAVE_OM, WAVEEPOCH = WXEPOCH and WAVEk = (-WXSIN_k,
+    -WXCOS_k)."""
+    from . import parameter as P
+    new = model.copy()
+    indices = [int(i) for i in model.get_wavex_indices("WaveX")]
+    oms = [(2.0 * np.pi * model[f"WXFREQ_{i:04d}"].value) / (i - 1 + 1.0) for i in indices]
+    if len(oms) > 1 and not np.allclose(oms, oms[0], atol=1e-3):
+        raise ValueError("This WaveX model cannot be properly translated into a Wave model due to the WaveX "
+                         "frequencies not producing a consistent WAVEOM value")
+    om = oms[0] if len(oms) == 1 else sum(oms) / len(oms)
+    amps = [(model[f"WXSIN_{i:04d}"].value, model[f"WXCOS_{i:04d}"].value) for i in indices]
+    epoch = model.WXEPOCH.value
+    _drop_component(new, "WaveX")
+    for n, v in (("WAVEEPOCH", None if epoch is None else P.LD(epoch)), ("WAVE_OM", float(om))):
+        p = P.make_param(n)
+        p.value = v
+        new.add_param(p)
+    for i, (s, c) in zip(indices, amps):
+        p = P.make_param(f"WAVE{i}")
+        p.value = (P.LD(s) * P.LD(-1.0), P.LD(c) * P.LD(-1.0))
+        new.add_param(p)
+    new.validate()
+    return new
 
 
 def _select(model, index, pick):

@@ -1,13 +1,14 @@
 """VGPRs, scratch and waves/SIMD of the library's kernels, from the compiler's resource remarks.
 
   hipcc <build()'s flags> -Rpass-analysis=kernel-resource-usage pint_amd/csrc/pint_hip.hip -o /tmp/x.so 2> new.txt
-  python scripts/diag/kernel_regs.py new.txt [old.txt] [name filter, default k_eval|k_glitch|k_wavex|k_fdjump]
+  python scripts/diag/kernel_regs.py new.txt [old.txt] [name filter, default k_eval|k_glitch|k_wavex|k_fdjump|k_phase_terms]
 
 With two files: every kernel of either whose name matches, side by side, and whether the figures
 are equal (the register gate of a change that must leave the evaluation's builds alone).  k_wavex
 is a template since the chromatic components: its plain build, k_wavex<false>, is compared with a
 parent's untemplated k_wavex; the chromatic build, k_wavex<true>, is listed as new.  k_fdjump
-(FDJump / FDJumpDM) is listed as new against a parent without it; "all" as the filter compares
+(FDJump / FDJumpDM) and k_phase_terms (PiecewiseSpindown / Wave / IFunc) are listed as new against a parent
+without them; "all" as the filter compares
 every kernel of the library.
 """
 import re
@@ -39,7 +40,7 @@ def demangle(names):
 
 if __name__ == "__main__":
     files = [a for a in sys.argv[1:] if a.endswith(".txt")]
-    rx = re.compile(([a for a in sys.argv[1:] if not a.endswith(".txt")] or ["k_eval|k_glitch|k_wavex|k_fdjump"])[0].replace("all", "."))
+    rx = re.compile(([a for a in sys.argv[1:] if not a.endswith(".txt")] or ["k_eval|k_glitch|k_wavex|k_fdjump|k_phase_terms"])[0].replace("all", "."))
     new = read(files[0])
     old = read(files[1]) if len(files) > 1 else None
     names = [n for n in dict.fromkeys(list(new) + list(old or {})) if rx.search(n)]
