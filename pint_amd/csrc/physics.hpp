@@ -1288,6 +1288,19 @@ struct ColRun {
     int dcol0;  // column in the compact fit layout (DMX columns are not stored there: -1)
     int pad_[3];
 };
+// the first column of a run in the layout in use (full: col0, compact fit layout: dcol0)
+PD long run_col(const ColRun& R, bool compact) { return compact ? R.dcol0 : R.col0; }
+// [u0, u1): the runs of one column kind.  A kind's columns are adjacent, so its runs are, and a
+// loop over a component's terms scans only those, at wave-uniform addresses; none: empty.
+PD void kind_runs(const ColRun* runs, int nrun, int kind, int& u0, int& u1) {
+    u0 = nrun;
+    u1 = 0;
+    for (int u = 0; u < nrun; u++)
+        if (runs[u].kind == kind) {
+            u0 = u < u0 ? u : u0;
+            u1 = u + 1;
+        }
+}
 
 // Evaluate one TOA.  If Mb != nullptr, writes the design-matrix row r (column-major,
 // leading dimension ld, column c at Mb + c*ld) for columns 0..ncol-1
@@ -1388,7 +1401,7 @@ PD void glitch_row_columns(const pint_spec_t& S, const double* P, dd tdb, double
     for (int u = 0; u < nrun; u++) {
         const ColRun R = runs[u];
         if (R.kind != PINT_COL_GLITCH) continue;
-        double* colp = Mb + (long)(compact ? R.dcol0 : R.col0) * ld;
+        double* colp = Mb + run_col(R, compact) * ld;
         for (int j = 0; j < R.cnt; j++, colp += ld) {
             const int k = (R.idx0 + j) / PINT_GL_NPAR, which = (R.idx0 + j) - PINT_GL_NPAR * k;
             const double gdt = glitch_dt(S, P, tdb, delay, k);
@@ -1434,7 +1447,7 @@ PD void pw_row_columns(const double* B0, dd tdb, double delay, double iF0, doubl
     for (int u = 0; u < nrun; u++) {
         const ColRun R = runs[u];
         if (R.kind != PINT_COL_PW) continue;
-        double* colp = Mb + (long)(compact ? R.dcol0 : R.col0) * ld;
+        double* colp = Mb + run_col(R, compact) * ld;
         for (int j = 0; j < R.cnt; j++, colp += ld) {
             const int k = (R.idx0 + j) >> 2, which = (R.idx0 + j) & 3;
             double dt;

@@ -18,6 +18,8 @@
 #include <cstring>
 #include <cstdio>
 #include <algorithm>
+#include <array>
+#include <utility>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -635,12 +637,47 @@ __device__ __forceinline__ void eval_block(int b, const PsrDev* __restrict__ psr
     }
 }
 
+// ---------------------------------------------------------------------------------
+// The passes around the evaluation.  A component that needs nothing the evaluation keeps in
+// registers is a row kernel of its own on the evaluation's inputs or outputs, so that no k_eval*
+// build carries its temporaries (inside the evaluation the glitch's exp and divisions, or the
+// solar wind's acos and sin, cost every build registers and the budgeted ones spills:
+// physics.hpp).  pint_eval launches them in this fixed order, each only for a batch in which
+// some model has the component (k_sw_geom: pint_ctx::d_swg; the passes after: pint_ctx::post):
+//
+//   k_sw_geom      before the evaluation.  Reads the rows' Sun vectors and the pulsar direction,
+//                  writes the solar-wind geometry that eval_pre and the NE_SW column read.
+//   k_eval*        delay, spindown phase, Taylor frequency, the design matrix but for the columns
+//                  below (zero-filled, the glitch columns left alone).
+//   k_wavex<CHROM> moves the delay: adds WaveX, DMWaveX (and ChromaticCM, CMWaveX), evaluated at
+//                  the evaluation's delay; writes the delay, the phase at it, the PINT_COL_WX /
+//                  DMWX / CM / CMWX columns.  One pass for the four so that a row's delay and
+//                  phase are read and written once and bfreq is formed once.
+//   k_fdjump       moves the delay: adds FDJump, FDJumpDM to what k_wavex left (neither reads the
+//                  accumulated delay); writes the delay, the phase at it, the PINT_COL_FDJUMP /
+//                  FDJUMPDM columns.  Its own pass so that no k_wavex build changes.
+//   k_glitch       adds phase only, at the final delay (so after the two that move it); writes
+//                  the phase and the PINT_COL_GLITCH columns.
+//   k_phase_terms  adds phase only, at the final delay: PiecewiseSpindown, Wave, IFunc; writes
+//                  the phase and the PINT_COL_PW columns.  Beside k_glitch, whose builds it
+//                  leaves alone.
+//
+// The delay-moving passes follow the order of the reference's DelayComponent_list (... binary,
+// WaveX, DMWaveX, ChromaticCM, CMWaveX, FDJump, FDJumpDM: see k_wavex); the phase-only ones
+// commute but for the dd rounding of the phase sum, so their order is fixed too.  A batch with
+// any pass after the evaluation runs its residual pass after the last of them, not fused into
+// the evaluation (efz).  Every pass: one thread per evaluation row (the TOAs and the TZR row,
+// r = n), grid (instances, row blocks of the longest instance), a block-uniform return for an
+// instance without the component, the instance's table read at block-uniform addresses; with
+// Mout the component's free columns of the TOAs' rows in the full or the compact fit layout.
+// The next component goes here: a kernel on post_row's frame, a bit of pint_ctx::post, a line
+// in pint_eval's sequence.
+// ---------------------------------------------------------------------------------
 // k_sw_geom: the solar-wind geometry (solar_wind_geometry_pc, pc) of every evaluation row (TOAs
 // and the TZR row) of the instances whose model has NE_SW, before the evaluation that reads it
 // (eval_pre's delay term, the NE_SW design-matrix column).  It depends on the TOA's Sun vector
-// and the pulsar direction (the per-instance constants) only.  A pass of its own: formed inside
-// k_eval, the acos / sin temporaries raised the register count of every build, spilling the
-// ones at a fixed budget.  Grid (instances, row blocks of the longest instance); ~40 B/row.
+// and the pulsar direction (the per-instance constants) only; ~40 B/row.  (No table, delay or
+// design matrix here, so it does not take the frame of the passes after the evaluation.)
 // (row i of a pulsar: a TOA or the TZR row; the pulsar direction at its epoch as eval_pre forms it)
 __device__ __forceinline__ double sw_geometry_row(const PsrDev& Pd, const InstConst& C, int i) {
     double L[3];
@@ -658,16 +695,100 @@ __global__ __launch_bounds__(256) void k_sw_geom(const PsrDev* __restrict__ psrs
     swg[I.roff + r] = sw_geometry_row(Pd, ic[blockIdx.x], r);
 }
 
-// k_wavex: the WaveX and DMWaveX components (wavex.py:365-396, dmwavex.py:355-387) of the
-// instances whose model has either, after the evaluation and before k_glitch (whose dt takes
-// the total delay), on the evaluation's outputs.  Both delays follow the binary's in the
-// reference's sum and need nothing the evaluation keeps in registers, so like the glitch they
-// are a pass of their own and no k_eval* build changes.  Per evaluation row (TOAs and the TZR
-// row) the kernel adds the WaveX delay, evaluated at the evaluation's delay D, and the DMWaveX
-// delay, writes the total delay back, moves the spindown phase to it, and with Mout writes the
-// free PINT_COL_WX / PINT_COL_DMWX columns (the evaluation has zeroed them) in the full or the
-// compact fit layout.  One thread per row; grid (instances, row blocks of the longest
-// instance); the harmonic loops read the instance's table at block-uniform addresses; one
+// The frame of a pass after the evaluation at its row: the instance, its pulsar, spec and table,
+// the row's TDB and delay so far, and where its design-matrix row goes.
+struct PostRow {
+    const InstDev I;
+    const PsrDev& Pd;
+    const pint_spec_t& S;
+    const double* P;  // the instance's table
+    int r;            // row: 0 ... n - 1 the TOAs, n the TZR row
+    dd tdb;
+    double D;    // the delay the evaluation and the passes before this one left
+    double* Mb;  // the instance's design matrix, null without it
+    bool wr;     // the row has a design-matrix row (a TOA)
+    bool cmp;    // the compact fit layout
+    long ld;     // leading dimension of Mb
+    __device__ __forceinline__ PostRow(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts)
+        : I(insts[blockIdx.x]), Pd(psrs[I.psr]), S(*Pd.spec) {}
+};
+// fills the row part; false for a thread past the TZR row.  (The kernel's own block-uniform
+// "nothing to do" return comes first, on F.Pd / F.S.)
+__device__ __forceinline__ bool post_row(PostRow& F, const double* __restrict__ tables,
+                                         const double* __restrict__ delay, double* __restrict__ Mout, int compact) {
+    F.r = blockIdx.y * 256 + threadIdx.x;
+    if (F.r > F.I.n) return false;
+    F.P = tables + F.I.toff;
+    F.tdb = dd_make(F.Pd.tdb_hi[F.r], F.Pd.tdb_lo[F.r]);
+    F.D = delay[F.I.roff + F.r];
+    F.Mb = Mout ? Mout + F.I.moff : nullptr;
+    F.wr = F.r < F.I.n;
+    F.cmp = compact && F.Pd.dsplit;
+    F.ld = F.I.n;
+    return true;
+}
+// the spin frequency at the row's dt (its delay so far, D): d_phase_d_delay = -F(dt), so the
+// columns of a delay component are M = -(d_phase_d_delay d_delay_d_p) / F0 = chain d_delay_d_p,
+// the chain factor of the evaluation's delay columns (F'(dt) d / F0 ~ 1e-22 apart at the new delay)
+__device__ __forceinline__ double post_chain(const pint_spec_t& S, const double* P, const InstConst& C, dd tdb,
+                                             double D, double& dtd, double& fdt) {
+    dtd = dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(P, S.o_PEPOCH)), DAYSEC), -D));
+    fdt = spin_freq(S, P, dtd);
+    return fdt * C.iF0;
+}
+// the barycentric radio frequency of row r (astrometry.py:359-364).  The evaluation keeps
+// 1 / bfreq^2 per row only on the shared-head path, so the passes form it again; eval_pre has its
+// own copy, on the direction and the velocity it already holds in registers.
+__device__ __forceinline__ double bary_freq_row(const PsrDev& Pd, const pint_spec_t& S, const InstConst& C, dd tdb,
+                                                int r) {
+    double bfreq = Pd.freq[r];
+    if (S.astrometry) {
+        double L[3];
+        psr_dir_icrs(C, dd_to_d(tdb), L);
+        const double vdl = Pd.vel[3 * r] * L[0] + Pd.vel[3 * r + 1] * L[1] + Pd.vel[3 * r + 2] * L[2];
+        bfreq *= 1.0 - vdl * INV_C_KMS;
+    }
+    return bfreq;
+}
+// The spindown phase moved to a new total delay: phase(dt - d) = phase(dt) - d F(dt)
+// + d^2 F'(dt) / 2 - ..., d = dsum the delay the pass added, dt the row's before it (dtd, fdt
+// = F(dt): post_chain).  The first-order term is always kept, as an exact product subtracted
+// in dd (F0 <= 1 kHz enters this term only: d F <= 1 cycle, whose rounding in dd is below 1e-30).
+//   SECOND false (WaveX, DMWaveX: d is tens of microseconds): the first dropped term,
+// d^2 |F'(dt)| / 2, is 5e-16 cycle at d = 1 ms and |F1| = 1e-9 Hz/s -- six orders below the
+// 1e-10 s x F0 phase bar.  No bound on d is checked.
+//   SECOND true (chromatic terms: a scattering delay at 400 MHz reaches milliseconds; FDJump,
+// tens of microseconds for real systems but a free-form value): + d^2 F'(dt) / 2 is kept too (in
+// double: at d = 1 s and |F1| = 1e-9 Hz/s it is 5e-10 cycle, its rounding 1e-25).  What is left:
+// the third-order term d^3 |F''| / 6 (2e-21 cycle at d = 1 s, |F2| = 1e-20 Hz/s^2), and the
+// rounding of F(dt) in the first-order product, 2^-53 d F = 1.1e-13 cycle at d = 1 s and F0 =
+// 1 kHz: below 1e-12 cycle for |d| <= 1 s (PINT_MAX_ADDED_DELAY).  A row beyond that sets the
+// PINT_E_PARAM bit of both status words and the call that checks the status fails.
+template <bool SECOND>
+__device__ __forceinline__ void post_move_phase(const PostRow& F, double* __restrict__ ph_hi,
+                                                double* __restrict__ ph_lo, double dsum, double dtd, double fdt,
+                                                int* __restrict__ status, int* __restrict__ istatus) {
+    const pint_spec_t& S = F.S;
+    const double* P = F.P;
+    dd ph = dd_sub(dd_make(ph_hi[F.I.roff + F.r], ph_lo[F.I.roff + F.r]), two_prod(dsum, fdt));
+    if (SECOND) {
+        double f1 = 0.0;
+        if (S.nf > 1) {
+            f1 = pval(P, S.o_F + 2 * (S.nf - 1));
+            for (int j = S.nf - 2; j >= 1; j--) f1 = f1 * dtd * inv_int(j) + pval(P, S.o_F + 2 * j);
+        }
+        ph = dd_add_d(ph, 0.5 * dsum * dsum * f1);
+        if (!(fabs(dsum) <= PINT_MAX_ADDED_DELAY)) {
+            atomicOr(status, 1 << PINT_E_PARAM);
+            atomicOr(istatus + blockIdx.x, 1 << PINT_E_PARAM);
+        }
+    }
+    ph_hi[F.I.roff + F.r] = ph.hi;
+    ph_lo[F.I.roff + F.r] = ph.lo;
+}
+
+// k_wavex: the WaveX and DMWaveX components (wavex.py:365-396, dmwavex.py:355-387).  Per row the
+// WaveX delay is evaluated at the evaluation's delay D, the DMWaveX delay without it; one
 // sincospi per harmonic serves the delay and the harmonic's two columns.
 //
 // sin and cos of a harmonic: the argument in half turns, x = 2 f (tdb - epoch), is formed in dd
@@ -707,22 +828,14 @@ __device__ __forceinline__ double wavex_harmonic(const double* H, dd dt_days, do
 // harmonic, ascending index -- one order of summation whatever is free, so a frozen amplitude
 // delays by the same bits), and with Mb the free columns of kind `kind`, scale * (sin | cos) a'_k,
 // from the same sincospi (Mb, ld, runs, compact as in eval_spin_b; wr: this row has a
-// design-matrix row).  A run's columns have consecutive indices 2 k + (0 sin, 1 cos); the kind's
-// runs are adjacent (its columns are), so each harmonic scans only those, at wave-uniform
-// addresses.
+// design-matrix row).  A run's columns have consecutive indices 2 k + (0 sin, 1 cos); each
+// harmonic scans only the kind's runs (kind_runs).
 template <bool ROT>
 __device__ __forceinline__ double wavex_component(const double* B, int nh, dd dt_days, double shift, int kind,
                                                   double scale, double* Mb, bool wr, unsigned r, long ld,
                                                   const ColRun* runs, int nrun, bool compact) {
     int u0 = 0, u1 = 0;
-    if (Mb) {
-        u0 = nrun;
-        for (int u = 0; u < nrun; u++)
-            if (runs[u].kind == kind) {
-                u0 = u < u0 ? u : u0;
-                u1 = u + 1;
-            }
-    }
+    if (Mb) kind_runs(runs, nrun, kind, u0, u1);
     double v = 0.0;
     for (int k = 0; k < nh; k++) {
         double s, c;
@@ -730,7 +843,7 @@ __device__ __forceinline__ double wavex_component(const double* B, int nh, dd dt
         for (int u = u0; u < u1; u++) {
             const ColRun R = runs[u];
             if (R.kind != kind) continue;
-            const long col = compact ? R.dcol0 : R.col0;
+            const long col = run_col(R, compact);
             const int js = 2 * k - R.idx0, jc = js + 1;
             if (wr && js >= 0 && js < R.cnt) Mb[(col + js) * ld + r] = scale * s;
             if (wr && jc >= 0 && jc < R.cnt) Mb[(col + jc) * ld + r] = scale * c;
@@ -764,46 +877,32 @@ __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, 
                                                double* __restrict__ delay, double* __restrict__ ph_hi,
                                                double* __restrict__ ph_lo, double* __restrict__ Mout, int compact,
                                                int* __restrict__ status, int* __restrict__ istatus) {
-    const InstDev I = insts[blockIdx.x];
-    const PsrDev& Pd = psrs[I.psr];
+    PostRow F(psrs, insts);
+    const PsrDev& Pd = F.Pd;
     const int nwx = Pd.nwx, ndmwx = Pd.ndmwx;
     const int ncm = CHROM ? Pd.ncm : 0, ncmwx = CHROM ? Pd.ncmwx : 0;
     if (nwx + ndmwx + ncm + ncmwx <= 0) return;  // (block-uniform)
-    const int r = blockIdx.y * 256 + threadIdx.x;
-    if (r > I.n) return;
-    const pint_spec_t& S = *Pd.spec;
-    const double* P = tables + I.toff;
+    if (!post_row(F, tables, delay, Mout, compact)) return;
+    const pint_spec_t& S = F.S;
+    const double* P = F.P;
     const InstConst& C = ic[blockIdx.x];
-    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
-    const double D = delay[I.roff + r];
-    // the spin frequency at the evaluation's dt (its delay D): d_phase_d_delay = -F(dt), so the
-    // columns are M = -(d_phase_d_delay d_delay_d_p) / F0 = chain d_delay_d_p, the chain factor
-    // of the other delay columns (F'(dt) d / F0 ~ 1e-22 apart at the new delay)
-    const double dtd = dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(P, S.o_PEPOCH)), DAYSEC), -D));
-    const double fdt = spin_freq(S, P, dtd);
-    const double chain = fdt * C.iF0;
-    double* Mb = Mout ? Mout + I.moff : nullptr;
-    const bool wr = r < I.n, cmp = compact && Pd.dsplit;
+    const int r = F.r;
+    const dd tdb = F.tdb;
+    const double D = F.D;
+    double* Mb = F.Mb;
+    const bool wr = F.wr, cmp = F.cmp;
+    double dtd, fdt;
+    const double chain = post_chain(S, P, C, tdb, D, dtd, fdt);
     double wx = 0.0, dmd = 0.0;
     if (nwx > 0)  // wavex_delay (wavex.py:365-380): the argument at tdb - WXEPOCH - D; the partials without D
         wx = wavex_component<true>(P + Pd.o_wx, nwx, dd_sub(tdb, pdd(P, Pd.o_wx - 2)), D * (1.0 / DAYSEC), PINT_COL_WX,
-                                   chain, Mb, wr, (unsigned)r, I.n, Pd.runs, Pd.nrun, cmp);
-    double bfreq = 0.0;
-    if (ndmwx > 0 || ncm + ncmwx > 0) {  // dmwavex_dm (dmwavex.py:355-368) * DMconst / bfreq^2 (dispersion_type_delay)
-        // the barycentric radio frequency, as eval_pre forms it (astrometry.py:359-364): the
-        // evaluation keeps 1 / bfreq^2 per row only on the shared-head path
-        bfreq = Pd.freq[r];
-        if (S.astrometry) {
-            double L[3];
-            psr_dir_icrs(C, dd_to_d(tdb), L);
-            const double vdl = Pd.vel[3 * r] * L[0] + Pd.vel[3 * r + 1] * L[1] + Pd.vel[3 * r + 2] * L[2];
-            bfreq *= 1.0 - vdl * INV_C_KMS;
-        }
-    }
-    if (ndmwx > 0) {
+                                   chain, Mb, wr, (unsigned)r, F.ld, Pd.runs, Pd.nrun, cmp);
+    // (only DMWaveX and the chromatic terms read the radio frequency)
+    const double bfreq = ndmwx > 0 || ncm + ncmwx > 0 ? bary_freq_row(Pd, S, C, tdb, r) : 0.0;
+    if (ndmwx > 0) {  // dmwavex_dm (dmwavex.py:355-368) * DMconst / bfreq^2 (dispersion_type_delay)
         const double dmscale = DMCONST / (bfreq * bfreq);
         dmd = wavex_component<false>(P + Pd.o_dmwx, ndmwx, dd_sub(tdb, pdd(P, Pd.o_dmwx - 2)), 0.0, PINT_COL_DMWX,
-                                     chain * dmscale, Mb, wr, (unsigned)r, I.n, Pd.runs, Pd.nrun, cmp) * dmscale;
+                                     chain * dmscale, Mb, wr, (unsigned)r, F.ld, Pd.runs, Pd.nrun, cmp) * dmscale;
     }
     double tot = (D + wx) + dmd;  // (the reference's order: ... binary, wavex, dmwavex)
     double dsum = wx + dmd;
@@ -821,10 +920,10 @@ __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, 
             for (int u = 0; u < Pd.nrun; u++) {
                 const ColRun R = Pd.runs[u];
                 if (R.kind != PINT_COL_CM) continue;
-                double* colp = Mb + (long)(cmp ? R.dcol0 : R.col0) * I.n;
+                double* colp = Mb + run_col(R, cmp) * F.ld;
                 double v = 1.0;
                 for (int j = 1; j <= R.idx0; j++) v = v * dty * inv_int(j);
-                for (int j = 0; j < R.cnt; j++, colp += I.n) {
+                for (int j = 0; j < R.cnt; j++, colp += F.ld) {
                     if (j > 0) v = v * dty * inv_int(R.idx0 + j);
                     colp[r] = cx * v;
                 }
@@ -834,51 +933,21 @@ __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, 
         dsum += cmd;
         if (ncmwx > 0) {  // cmwavex_cm (cmwavex.py:355-368) * X
             const double cmwd = wavex_component<false>(P + Pd.o_cmwx, ncmwx, dd_sub(tdb, pdd(P, Pd.o_cmwx - 2)), 0.0,
-                                                       PINT_COL_CMWX, chain * X, Mb, wr, (unsigned)r, I.n, Pd.runs,
+                                                       PINT_COL_CMWX, chain * X, Mb, wr, (unsigned)r, F.ld, Pd.runs,
                                                        Pd.nrun, cmp) * X;
             tot += cmwd;
             dsum += cmwd;
         }
     }
-    delay[I.roff + r] = tot;
-    // The spindown phase at the new total delay: phase(dt - d) = phase(dt) - d F(dt) + d^2 F'(dt) / 2
-    // - ..., d = wx + dmd, dt the evaluation's.  The first-order term is kept, as an exact product
-    // added in dd; the first dropped term, d^2 |F'(dt)| / 2, is 5e-16 cycle at d = 1 ms and
-    // |F1| = 1e-9 Hz/s (F0 <= 1 kHz enters the kept term only: d F <= 1 cycle, whose rounding in dd
-    // is below 1e-30) -- six orders below the 1e-10 s x F0 phase bar; d itself is tens of
-    // microseconds.
-    dd ph = dd_sub(dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]), two_prod(dsum, fdt));
-    if (CHROM && ncm + ncmwx > 0) {
-        // With chromatic terms d = wavex + dmwavex + cm + cmwavex is no longer tens of microseconds
-        // (a scattering delay at 400 MHz reaches milliseconds), so the second-order term
-        // + d^2 F'(dt) / 2 is kept (in double: at d = 1 s and |F1| = 1e-9 Hz/s it is 5e-10 cycle,
-        // its rounding 1e-25).  What is left: the third-order term d^3 |F''| / 6 (2e-21 cycle at
-        // d = 1 s, |F2| = 1e-20 Hz/s^2), and the rounding of F(dt) in the kept first-order product,
-        // 2^-53 d F = 1.1e-13 cycle at d = 1 s and F0 = 1 kHz: below 1e-12 cycle for |d| <= 1 s
-        // (PINT_MAX_ADDED_DELAY).  A row beyond that sets the PINT_E_PARAM status bit and the call
-        // that checks the status fails; pulsars without chromatic terms take the first-order
-        // form above, bit for bit the plain build's.
-        double f1 = 0.0;
-        if (S.nf > 1) {
-            f1 = pval(P, S.o_F + 2 * (S.nf - 1));
-            for (int j = S.nf - 2; j >= 1; j--) f1 = f1 * dtd * inv_int(j) + pval(P, S.o_F + 2 * j);
-        }
-        ph = dd_add_d(ph, 0.5 * dsum * dsum * f1);
-        if (!(fabs(dsum) <= PINT_MAX_ADDED_DELAY)) {
-            atomicOr(status, 1 << PINT_E_PARAM);
-            atomicOr(istatus + blockIdx.x, 1 << PINT_E_PARAM);
-        }
-    }
-    ph_hi[I.roff + r] = ph.hi;
-    ph_lo[I.roff + r] = ph.lo;
+    delay[F.I.roff + r] = tot;
+    // the second-order form and the bound only on the rows of pulsars with chromatic terms: the
+    // others take the first-order form, bit for bit the plain build's
+    if (CHROM && ncm + ncmwx > 0) post_move_phase<true>(F, ph_hi, ph_lo, dsum, dtd, fdt, status, istatus);
+    else post_move_phase<false>(F, ph_hi, ph_lo, dsum, dtd, fdt, status, istatus);
 }
 
-// k_fdjump: the FDJump and FDJumpDM components (fdjump.py:122-193, dispersion_model.py:859-884) of
-// the instances whose model has either (pint_set_fdjump), after k_wavex and before k_glitch (whose
-// dt takes the total delay), on the evaluation's outputs.  Neither delay reads the accumulated
-// delay, so like the other post-evaluation components they are a pass of their own and no
-// k_eval* or k_wavex build changes.  Per evaluation row (TOAs and the TZR row), with bfreq the
-// barycentric radio frequency as k_wavex forms it:
+// k_fdjump: the FDJump and FDJumpDM components (fdjump.py:122-193, dispersion_model.py:859-884,
+// pint_set_fdjump).  Per row, with bfreq the barycentric radio frequency:
 //   FDJump    y = log(bfreq / 1 GHz) (FDJUMPLOG Y, the constructor's value) or bfreq / 1 GHz, a
 //             non-finite y replaced by 0 (get_freq_y, :122-150); delay = sum_k [row selected by
 //             parameter k's mask] value_k y^p_k; overlapping masks add (:165-173);
@@ -886,50 +955,33 @@ __global__ __launch_bounds__(256) void k_wavex(const PsrDev* __restrict__ psrs, 
 // The reference's DelayComponent_list ends ... WaveX, DMWaveX, ChromaticCM, CMWaveX, FDJump,
 // FDJumpDM in the run the fixtures were captured in (fdjump and fdjumpdm are not categories of
 // DEFAULT_ORDER either: see k_wavex); the total is ((D + fdjump) + fdjumpdm), D what k_wavex left.
-// One thread per row; grid (instances, row blocks of the longest instance).  The parameter loops
-// are wave-uniform: value and FD index come from the table and the descriptor at uniform
-// addresses, the block is sorted by FD index so one running power of y serves every parameter,
-// and the add is predicated on the row's mask bit (no per-lane loop over set bits).  With Mout
-// every row of every free PINT_COL_FDJUMP / PINT_COL_FDJUMPDM column is written, chain * y^p or
-// chain * (-DMconst / bfreq^2) on the selected rows and 0 on the others (coalesced; nothing relies
-// on the evaluation's zero fill), in the full or the compact fit layout.  A kind's runs are
-// adjacent (its columns are), so each parameter scans only those.
-//
-// Phase: moved to the new total delay as k_wavex<true> does, phase(dt - d) = phase(dt) - d F(dt)
-// + d^2 F'(dt) / 2 with d = fdjump + fdjumpdm (tens of microseconds for real systems), the
-// first-order product exact in dd; the same bound |d| <= PINT_MAX_ADDED_DELAY holds 1e-12 cycle
-// and a row beyond it sets the PINT_E_PARAM status bits.
+// The parameter loops are wave-uniform: value and FD index come from the table and the descriptor
+// at uniform addresses, the block is sorted by FD index so one running power of y serves every
+// parameter, and the add is predicated on the row's mask bit (no per-lane loop over set bits).
+// With Mout every row of every free PINT_COL_FDJUMP / PINT_COL_FDJUMPDM column is written,
+// chain * y^p or chain * (-DMconst / bfreq^2) on the selected rows and 0 on the others (coalesced;
+// nothing relies on the evaluation's zero fill); each parameter scans only its kind's runs
+// (kind_runs).  The phase moves in the second-order form, d = fdjump + fdjumpdm (post_move_phase).
 __global__ __launch_bounds__(256) void k_fdjump(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
                                                 const double* __restrict__ tables, const InstConst* __restrict__ ic,
                                                 double* __restrict__ delay, double* __restrict__ ph_hi,
                                                 double* __restrict__ ph_lo, double* __restrict__ Mout, int compact,
                                                 int* __restrict__ status, int* __restrict__ istatus) {
-    const InstDev I = insts[blockIdx.x];
-    const PsrDev& Pd = psrs[I.psr];
+    PostRow F(psrs, insts);
+    const PsrDev& Pd = F.Pd;
     const int nfdj = Pd.nfdj, nfdjdm = Pd.nfdjdm;
     if (nfdj + nfdjdm <= 0) return;  // (block-uniform)
-    const int r = blockIdx.y * 256 + threadIdx.x;
-    if (r > I.n) return;
-    const pint_spec_t& S = *Pd.spec;
-    const double* P = tables + I.toff;
+    if (!post_row(F, tables, delay, Mout, compact)) return;
+    const double* P = F.P;
     const InstConst& C = ic[blockIdx.x];
-    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
-    const double D = delay[I.roff + r];
-    // the spin frequency at the row's delay so far: the chain factor of the delay columns (k_wavex)
-    const double dtd = dd_to_d(dd_add_d(dd_mul_d(dd_sub(tdb, pdd(P, S.o_PEPOCH)), DAYSEC), -D));
-    const double fdt = spin_freq(S, P, dtd);
-    const double chain = fdt * C.iF0;
-    double* Mb = Mout ? Mout + I.moff : nullptr;
-    const bool wr = Mb && r < I.n, cmp = compact && Pd.dsplit;
-    const long ld = I.n;
-    // the barycentric radio frequency, as eval_pre and k_wavex form it (astrometry.py:359-364)
-    double bfreq = Pd.freq[r];
-    if (S.astrometry) {
-        double L[3];
-        psr_dir_icrs(C, dd_to_d(tdb), L);
-        const double vdl = Pd.vel[3 * r] * L[0] + Pd.vel[3 * r + 1] * L[1] + Pd.vel[3 * r + 2] * L[2];
-        bfreq *= 1.0 - vdl * INV_C_KMS;
-    }
+    const int r = F.r;
+    const double D = F.D;
+    double* Mb = F.Mb;
+    const bool wr = F.wr, cmp = F.cmp;
+    const long ld = F.ld;
+    double dtd, fdt;
+    const double chain = post_chain(F.S, P, C, F.tdb, D, dtd, fdt);
+    const double bfreq = bary_freq_row(Pd, F.S, C, F.tdb, r);
     const ColRun* runs = Pd.runs;
     const int nrun = Pd.nrun;
     double fd = 0.0, dmd = 0.0;
@@ -938,14 +990,7 @@ __global__ __launch_bounds__(256) void k_fdjump(const PsrDev* __restrict__ psrs,
         if (np <= 0) continue;
         const int kind = fam ? PINT_COL_FDJUMPDM : PINT_COL_FDJUMP;
         int u0 = 0, u1 = 0;
-        if (Mb) {
-            u0 = nrun;
-            for (int u = 0; u < nrun; u++)
-                if (runs[u].kind == kind) {
-                    u0 = u < u0 ? u : u0;
-                    u1 = u + 1;
-                }
-        }
+        if (Mb) kind_runs(runs, nrun, kind, u0, u1);
         const unsigned long long m = (fam ? Pd.fdjdmmask : Pd.fdjmask)[r];
         const double* B = P + (fam ? Pd.o_fdjdm : Pd.o_fdj);
         double y = 0.0, yp = 0.0;  // yp: y^p at the current FD index p; FDJumpDM: the column value
@@ -968,98 +1013,68 @@ __global__ __launch_bounds__(256) void k_fdjump(const PsrDev* __restrict__ psrs,
                 const ColRun R = runs[u];
                 if (R.kind != kind) continue;
                 const int j = k - R.idx0;
-                if (wr && j >= 0 && j < R.cnt) Mb[((long)(cmp ? R.dcol0 : R.col0) + j) * ld + r] = sel ? chain * yp : 0.0;
+                if (wr && j >= 0 && j < R.cnt) Mb[(run_col(R, cmp) + j) * ld + r] = sel ? chain * yp : 0.0;
             }
         }
         if (fam) dmd = acc * DMCONST / (bfreq * bfreq);  // dispersion_time_delay (dispersion_model.py:42-52)
         else fd = acc;
     }
     const double dsum = fd + dmd;
-    delay[I.roff + r] = (D + fd) + dmd;
-    double f1 = 0.0;
-    if (S.nf > 1) {
-        f1 = pval(P, S.o_F + 2 * (S.nf - 1));
-        for (int j = S.nf - 2; j >= 1; j--) f1 = f1 * dtd * inv_int(j) + pval(P, S.o_F + 2 * j);
-    }
-    dd ph = dd_sub(dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]), two_prod(dsum, fdt));
-    ph = dd_add_d(ph, 0.5 * dsum * dsum * f1);
-    if (!(fabs(dsum) <= PINT_MAX_ADDED_DELAY)) {
-        atomicOr(status, 1 << PINT_E_PARAM);
-        atomicOr(istatus + blockIdx.x, 1 << PINT_E_PARAM);
-    }
-    ph_hi[I.roff + r] = ph.hi;
-    ph_lo[I.roff + r] = ph.lo;
+    delay[F.I.roff + r] = (D + fd) + dmd;
+    post_move_phase<true>(F, ph_hi, ph_lo, dsum, dtd, fdt, status, istatus);
 }
 
-// k_glitch: the Glitch component (glitch.py:193-344) of the instances whose model has glitches,
-// after the evaluation, on its outputs: every evaluation row's phase (TOAs and the TZR row)
-// gains the glitch phase at the row's total delay, and with Mout the PINT_COL_GLITCH columns of
-// the TOAs' rows are written (the evaluation leaves them alone), in the full or the compact fit
-// layout.  A pass of its own because inside k_eval / k_eval_spin the exp and the divisions cost
-// those builds registers and occupancy (physics.hpp); a batch with glitches therefore runs its
-// residual pass after this kernel, not fused into the evaluation.  The same tables and
-// per-instance constants as the evaluation.  One thread per row; grid (instances, row blocks
-// of the longest instance); ~50 B/row plus 8 B per free glitch column.
+// k_glitch: the Glitch component (glitch.py:193-344): every row's phase gains the glitch phase at
+// the row's total delay; the evaluation leaves the PINT_COL_GLITCH columns alone, so with Mout the
+// TOAs' rows of each are written here.  ~50 B/row plus 8 B per free glitch column.
 __global__ __launch_bounds__(256) void k_glitch(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
                                                 const double* __restrict__ tables, const InstConst* __restrict__ ic,
                                                 const double* __restrict__ delay, double* __restrict__ ph_hi,
                                                 double* __restrict__ ph_lo, double* __restrict__ Mout, int compact) {
-    const InstDev I = insts[blockIdx.x];
-    const PsrDev& Pd = psrs[I.psr];
-    const pint_spec_t& S = *Pd.spec;
-    if (S.nglitch <= 0) return;  // (block-uniform)
-    const int r = blockIdx.y * 256 + threadIdx.x;
-    if (r > I.n) return;
-    const double* P = tables + I.toff;
-    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
-    const double dl = delay[I.roff + r];
-    const dd ph = glitch_row_phase(S, P, tdb, dl, dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]));
-    ph_hi[I.roff + r] = ph.hi;
-    ph_lo[I.roff + r] = ph.lo;
-    if (Mout && r < I.n)
-        glitch_row_columns(S, P, tdb, dl, ic[blockIdx.x].iF0, Mout + I.moff, (unsigned)r, I.n, Pd.runs, Pd.nrun,
-                           compact && Pd.dsplit);
+    PostRow F(psrs, insts);
+    if (F.S.nglitch <= 0) return;  // (block-uniform)
+    if (!post_row(F, tables, delay, Mout, compact)) return;
+    const long o = F.I.roff + F.r;
+    const dd ph = glitch_row_phase(F.S, F.P, F.tdb, F.D, dd_make(ph_hi[o], ph_lo[o]));
+    ph_hi[o] = ph.hi;
+    ph_lo[o] = ph.lo;
+    if (F.Mb && F.wr)
+        glitch_row_columns(F.S, F.P, F.tdb, F.D, ic[blockIdx.x].iF0, F.Mb, (unsigned)F.r, F.ld, F.Pd.runs, F.Pd.nrun,
+                           F.cmp);
 }
 
 // k_phase_terms: the PiecewiseSpindown, Wave and IFunc components (piecewise.py:181-253,
-// wave.py:148-168, ifunc.py:113-148) of the instances whose model has any of them
-// (pint_set_phase_terms), after k_wavex and k_fdjump (which move the delay) and beside k_glitch,
-// in k_glitch's form: every evaluation row's phase (TOAs and the TZR row) gains the three
+// wave.py:148-168, ifunc.py:113-148, pint_set_phase_terms): every row's phase gains the three
 // components' phases at the row's total delay, and with Mout the PINT_COL_PW columns of the TOAs'
-// rows are written (the evaluation leaves them zero), in the full or the compact fit layout.
-// None of the three registers a derivative with respect to the delay, so no other column moves.
-// A batch with them runs its residual pass after this kernel, not fused into the evaluation.
-// One thread per row; grid (instances, row blocks of the longest instance); the pieces and the
-// Wave terms are read at block-uniform addresses, IFunc's points by a per-row binary search
-// (physics.hpp); no LDS, no atomics.  ~50 B/row plus 8 B per free piece column.
+// rows are written (the evaluation leaves them zero).  None of the three registers a derivative
+// with respect to the delay, so no other column moves.  The pieces and the Wave terms are read at
+// block-uniform addresses, IFunc's points by a per-row binary search (physics.hpp); no LDS, no
+// atomics.  ~50 B/row plus 8 B per free piece column.
 __global__ __launch_bounds__(256) void k_phase_terms(const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts,
                                                      const double* __restrict__ tables,
                                                      const InstConst* __restrict__ ic,
                                                      const double* __restrict__ delay, double* __restrict__ ph_hi,
                                                      double* __restrict__ ph_lo, double* __restrict__ Mout,
                                                      int compact) {
-    const InstDev I = insts[blockIdx.x];
-    const PsrDev& Pd = psrs[I.psr];
+    PostRow F(psrs, insts);
+    const PsrDev& Pd = F.Pd;
     const int npw = Pd.npw, nwave = Pd.nwave, nif = Pd.nifunc;
     if (npw + nwave + nif <= 0) return;  // (block-uniform)
-    const int r = blockIdx.y * 256 + threadIdx.x;
-    if (r > I.n) return;
-    const double* P = tables + I.toff;
-    const dd tdb = dd_make(Pd.tdb_hi[r], Pd.tdb_lo[r]);
-    const double dl = delay[I.roff + r];
-    dd ph = dd_make(ph_hi[I.roff + r], ph_lo[I.roff + r]);
-    if (npw > 0) ph = pw_row_phase(P + Pd.o_pw, npw, tdb, dl, ph);
+    if (!post_row(F, tables, delay, Mout, compact)) return;
+    const double* P = F.P;
+    const long o = F.I.roff + F.r;
+    dd ph = dd_make(ph_hi[o], ph_lo[o]);
+    if (npw > 0) ph = pw_row_phase(P + Pd.o_pw, npw, F.tdb, F.D, ph);
     // Wave and IFunc: seconds, summed and turned into cycles by F0 (a few cycles at most: the
     // product in double rounds at 1e-16 cycle)
     double times = 0.0;
-    if (nwave > 0) times += wave_times(P + Pd.o_wave, nwave, tdb, dl);
-    if (nif > 0) times += ifunc_times(Pd.ifx_hi, Pd.ifx_lo, Pd.ify, nif, Pd.sifunc, tdb, dl);
-    if (nwave + nif > 0) ph = dd_add_d(ph, pval(P, Pd.spec->o_F) * times);
-    ph_hi[I.roff + r] = ph.hi;
-    ph_lo[I.roff + r] = ph.lo;
-    if (Mout && npw > 0 && r < I.n)
-        pw_row_columns(P + Pd.o_pw, tdb, dl, ic[blockIdx.x].iF0, Mout + I.moff, (unsigned)r, I.n, Pd.runs, Pd.nrun,
-                       compact && Pd.dsplit);
+    if (nwave > 0) times += wave_times(P + Pd.o_wave, nwave, F.tdb, F.D);
+    if (nif > 0) times += ifunc_times(Pd.ifx_hi, Pd.ifx_lo, Pd.ify, nif, Pd.sifunc, F.tdb, F.D);
+    if (nwave + nif > 0) ph = dd_add_d(ph, pval(P, F.S.o_F) * times);
+    ph_hi[o] = ph.hi;
+    ph_lo[o] = ph.lo;
+    if (F.Mb && npw > 0 && F.wr)
+        pw_row_columns(P + Pd.o_pw, F.tdb, F.D, ic[blockIdx.x].iF0, F.Mb, (unsigned)F.r, F.ld, Pd.runs, Pd.nrun, F.cmp);
 }
 
 // Spin-only grids (pint_set_grid's variables all spin frequencies, isolated model, no
@@ -1202,6 +1217,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) voi
     WgTimer wgt_(WGT_EVAL);
     eval_mix_body<WANT_M>(PINT_EVAL_MIX_PASS);
 }
+// the k_eval build of every block kind at the compiler's own register allocation, [with M][kind]
+// (the builds at a register budget are pint_eval's special cases)
+using EvalKernel = decltype(&k_eval<0, 0>);
+using EvalMixKernel = decltype(&k_eval_mix<0>);
+template <int WM, size_t... BT>
+constexpr std::array<EvalKernel, sizeof...(BT)> eval_kernel_row(std::index_sequence<BT...>) {
+    return {{k_eval<WM, (int)BT>...}};
+}
+constexpr std::array<EvalKernel, PINT_NBLK> EVAL_KERNELS[2] = {
+    eval_kernel_row<0>(std::make_index_sequence<PINT_NBLK>{}), eval_kernel_row<1>(std::make_index_sequence<PINT_NBLK>{})};
 
 // ---------------------------------------------------------------------------------
 // k_resid1/k_resid2 — residuals.py:314-425, :483-538, :638-667
@@ -5975,6 +6000,16 @@ struct PsrHost {
     double f1 = 0.0, f1_lo = 0.0;  // the red-noise fundamental (dd), k_trig_setup
 };
 
+// pint_ctx::post: some instance of the batch has the component, so its pass follows the
+// evaluation (the order of the launches: pint_eval)
+enum : unsigned {
+    POST_WAVEX = 1,        // WaveX / DMWaveX, or chromatic terms: k_wavex
+    POST_CHROM = 2,        // ChromaticCM / CMWaveX: k_wavex<true> instead of the plain build (POST_WAVEX is set too)
+    POST_FDJUMP = 4,       // FDJump / FDJumpDM: k_fdjump
+    POST_GLITCH = 8,       // Glitch: k_glitch
+    POST_PHASE_TERMS = 16  // PiecewiseSpindown / Wave / IFunc: k_phase_terms
+};
+
 struct pint_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -6048,11 +6083,7 @@ struct pint_ctx {
     double* d_rpart = nullptr;    // per residual block: sum w, sum w x, chi2 partial
     double* d_epart = nullptr;    // fused residual pass (efz): per evaluation block sum w, sum w x
     int efz = 0;                  // the batch's evaluation blocks carry k_resid1 (EF_ROWS rows + row 0 + TZR)
-    bool any_glitch = false;      // an instance's model has glitches: k_glitch follows the evaluation
-    bool any_wavex = false;       // ... has WaveX or DMWaveX: k_wavex follows the evaluation (before k_glitch)
-    bool any_chrom = false;       // ... has ChromaticCM / CMWaveX: k_wavex<true> instead (any_wavex is set too)
-    bool any_fdjump = false;      // ... has FDJump / FDJumpDM: k_fdjump follows k_wavex (before k_glitch)
-    bool any_phase_terms = false; // ... has PiecewiseSpindown / Wave / IFunc: k_phase_terms follows k_fdjump
+    unsigned post = 0;  // POST_*: the passes that follow the batch's evaluation (set_instances_impl)
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
@@ -7513,35 +7544,19 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     // the fused residual pass for batches off the small-instance path (whose one-wave
     // residual kernels serve instances of <= RES_SMALLN rows)
     // (not for a batch with glitches: their phase is added after the evaluation, by k_glitch)
-    ctx->any_glitch = false;
-    for (int k = 0; k < ninst; k++) ctx->any_glitch = ctx->any_glitch || ctx->psrs[inst_psr[k]].spec.nglitch > 0;
-    // (nor with WaveX / DMWaveX: k_wavex moves the delay and the phase after the evaluation)
-    ctx->any_wavex = false;
+    // nor with any pass after the evaluation: k_wavex and k_fdjump move the delay and the phase,
+    // k_glitch and k_phase_terms add phase, all after the evaluation's blocks have finished
+    ctx->post = 0;
     for (int k = 0; k < ninst; k++) {
-        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
-        ctx->any_wavex = ctx->any_wavex || d.nwx + d.ndmwx > 0;
+        const PsrHost& e = ctx->psrs[inst_psr[k]];
+        const PsrDev& d = e.dev;
+        if (d.nwx + d.ndmwx > 0) ctx->post |= POST_WAVEX;
+        if (d.ncm + d.ncmwx > 0) ctx->post |= POST_WAVEX | POST_CHROM;  // (the same pass, in its chromatic build)
+        if (d.nfdj + d.nfdjdm > 0) ctx->post |= POST_FDJUMP;
+        if (e.spec.nglitch > 0) ctx->post |= POST_GLITCH;
+        if (d.npw + d.nwave + d.nifunc > 0) ctx->post |= POST_PHASE_TERMS;
     }
-    // (nor with chromatic terms: the same pass, in its chromatic build)
-    ctx->any_chrom = false;
-    for (int k = 0; k < ninst; k++) {
-        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
-        ctx->any_chrom = ctx->any_chrom || d.ncm + d.ncmwx > 0;
-    }
-    ctx->any_wavex = ctx->any_wavex || ctx->any_chrom;
-    // (nor with FDJump / FDJumpDM: k_fdjump moves the delay and the phase after the evaluation)
-    ctx->any_fdjump = false;
-    for (int k = 0; k < ninst; k++) {
-        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
-        ctx->any_fdjump = ctx->any_fdjump || d.nfdj + d.nfdjdm > 0;
-    }
-    // (nor with PiecewiseSpindown / Wave / IFunc: k_phase_terms adds their phase after the evaluation)
-    ctx->any_phase_terms = false;
-    for (int k = 0; k < ninst; k++) {
-        const PsrDev& d = ctx->psrs[inst_psr[k]].dev;
-        ctx->any_phase_terms = ctx->any_phase_terms || d.npw + d.nwave + d.nifunc > 0;
-    }
-    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && !ctx->any_glitch && !ctx->any_wavex &&
-               !ctx->any_fdjump && !ctx->any_phase_terms;
+    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && ctx->post == 0;
     long ebn = 0;
     // N-split for the Gram so the launch fills the 256 CUs
     // choose the split count that minimises (workgroup rounds) / nsplit, i.e. the k_gram
@@ -8161,6 +8176,10 @@ static void flush_r2(pint_ctx* ctx) {
     launch_resid2(ctx, false);
 }
 
+// the grid of a row pass (k_sw_geom and the passes after the evaluation): instances x 256-row
+// blocks of the longest instance's n + 1 rows
+static dim3 pass_grid(const pint_ctx* ctx, int ninst) { return dim3(ninst, (ctx->maxn + 256) / 256); }
+
 int pint_eval(pint_ctx* ctx, int want_M) {
     if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
     hipSetDevice(ctx->device);
@@ -8209,8 +8228,8 @@ int pint_eval(pint_ctx* ctx, int want_M) {
                            !ctx->efz && ctx->d_shr && ctx->blk_off[PINT_NBLK] == ctx->blk_off[1];
     if (ctx->d_swg) {  // SolarWindDispersion: the rows' geometry at these constants, read by the evaluation
         // (the shared head reads the first point's rows only)
-        hipLaunchKernelGGL(k_sw_geom, dim3(spin_pass ? 1 : ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream,
-                           ctx->d_psrs, ctx->d_inst, icp, ctx->d_swg);
+        hipLaunchKernelGGL(k_sw_geom, pass_grid(ctx, spin_pass ? 1 : ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, icp, ctx->d_swg);
         HIPCHK(hipGetLastError());
         rs.swg = ctx->d_swg;
     }
@@ -8231,27 +8250,17 @@ int pint_eval(pint_ctx* ctx, int want_M) {
     for (int t = 0; t < 3; t++) ntyp += ctx->blk_off[t + 1] > ctx->blk_off[t];
     const bool mix = ((ctx->eval_merge >> (want_M ? 1 : 0)) & 1) && (ntyp > 1 || (ctx->eval_merge & 4));
     if (!spin_pass && mix && ctx->nblk > 0) {
-#define PINT_EVAL_MIX(WM)                                                                                      \
-        hipLaunchKernelGGL((k_eval_mix<WM>), dim3(ctx->nblk), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, \
-                           ctx->d_blk_inst, ctx->d_blk_row0, ctx->blk_off[1], ctx->blk_off[2], ctx->blk_off[3],   \
-                           tabs, icp, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, \
-                           ctx->d_dmxv, want_M == 2 ? 1 : 0, write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs)
         // the 3-waves/SIMD register budget (spills) pays when the blocks fill the SIMDs more
         // than twice; a small batch (<= 2 waves per SIMD) runs the unconstrained build (203
         // VGPRs, no spills) at its own occupancy
         const bool small = ctx->nblk <= 2 * 256;
-        if (want_M && ctx->eval_wpe == 3 && !small) {
-            hipLaunchKernelGGL((k_eval_mix_w<1, 3>), dim3(ctx->nblk), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_blk_inst, ctx->d_blk_row0, ctx->blk_off[1], ctx->blk_off[2], ctx->blk_off[3],
-                               tabs, icp, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M,
-                               ctx->d_dmxv, want_M == 2 ? 1 : 0, write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs);
-        } else if (want_M && ctx->eval_wpe == 4) {
-            hipLaunchKernelGGL((k_eval_mix_w<1, 4>), dim3(ctx->nblk), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_blk_inst, ctx->d_blk_row0, ctx->blk_off[1], ctx->blk_off[2], ctx->blk_off[3],
-                               tabs, icp, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M,
-                               ctx->d_dmxv, want_M == 2 ? 1 : 0, write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs);
-        } else if (want_M) PINT_EVAL_MIX(1); else PINT_EVAL_MIX(0);
-#undef PINT_EVAL_MIX
+        EvalMixKernel kern = want_M ? k_eval_mix<1> : k_eval_mix<0>;
+        if (want_M && ctx->eval_wpe == 3 && !small) kern = k_eval_mix_w<1, 3>;
+        else if (want_M && ctx->eval_wpe == 4) kern = k_eval_mix_w<1, 4>;
+        hipLaunchKernelGGL(kern, dim3(ctx->nblk), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_blk_inst,
+                           ctx->d_blk_row0, ctx->blk_off[1], ctx->blk_off[2], ctx->blk_off[3], tabs, icp, ctx->d_phhi,
+                           ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, ctx->d_dmxv, want_M == 2 ? 1 : 0, write_red,
+                           ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs);
         HIPCHK(hipGetLastError());
     }
     // one launch per binary model, back to back on the stream: all models without the merged
@@ -8263,82 +8272,40 @@ int pint_eval(pint_ctx* ctx, int want_M) {
         if (nb == 0) continue;
         const int* bi = ctx->d_blk_inst + ctx->blk_off[t];
         const int* br = ctx->d_blk_row0 + ctx->blk_off[t];
-#define PINT_EVAL_LAUNCH(WM, BT, ...)                                                                     \
-        hipLaunchKernelGGL((k_eval<WM, BT, ##__VA_ARGS__>), dim3(nb), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, bi, br, \
-                           tabs, icp, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, \
-                           ctx->d_dmxv, want_M == 2 ? 1 : 0, write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs)
+        EvalKernel kern = EVAL_KERNELS[want_M != 0][t];
         // the isolated build at a register budget of 6 waves/SIMD with M (80 VGPRs, no spills:
         // 0.28 vs 0.31 ms on the 65,536-point NGC6440E grid) and 8 without (64 VGPRs, 36 B of
         // spills: 0.143 vs 0.162 ms); 8 with M spilled 76 B and lost (0.35 ms).
         // PINT_EVAL0_WPE=0: the compiler's own allocation (84 / 74 VGPRs, 5 / 6 waves)
         if (t == 0 && ctx->eval0_wpe) {
-            if (want_M) PINT_EVAL_LAUNCH(1, 0, 6); else PINT_EVAL_LAUNCH(0, 0, 8);
+            kern = want_M ? k_eval<1, 0, 6> : k_eval<0, 0, 8>;
         } else if (want_M && (t == 1 || t == 2) && ctx->evalb_wpe == 3 && nb > 2 * 256) {
             // a large one-model ELL1 or DD batch (a J0740 grid) with M at the merged build's
             // budget of 3 waves/SIMD (168 VGPRs + spills) instead of 2 (174 / 202 VGPRs)
-            if (t == 1) PINT_EVAL_LAUNCH(1, 1, 3); else PINT_EVAL_LAUNCH(1, 2, 3);
-        } else if (want_M) {
-            switch (t) {
-                case 0: PINT_EVAL_LAUNCH(1, 0); break;
-                case 1: PINT_EVAL_LAUNCH(1, 1); break;
-                case 2: PINT_EVAL_LAUNCH(1, 2); break;
-                case 3: PINT_EVAL_LAUNCH(1, 3); break;
-                case 4: PINT_EVAL_LAUNCH(1, 4); break;
-                case 5: PINT_EVAL_LAUNCH(1, 5); break;
-                case 6: PINT_EVAL_LAUNCH(1, 6); break;
-                case 7: PINT_EVAL_LAUNCH(1, 7); break;
-                case 8: PINT_EVAL_LAUNCH(1, 8); break;
-                case PINT_BLK_FB_ELL1: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_ELL1); break;
-                case PINT_BLK_FB_DD: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_DD); break;
-                case PINT_BLK_FB_ELL1H: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_ELL1H); break;
-                default: PINT_EVAL_LAUNCH(1, PINT_BLK_FB_BT); break;
-            }
-        } else {
-            switch (t) {
-                case 0: PINT_EVAL_LAUNCH(0, 0); break;
-                case 1: PINT_EVAL_LAUNCH(0, 1); break;
-                case 2: PINT_EVAL_LAUNCH(0, 2); break;
-                case 3: PINT_EVAL_LAUNCH(0, 3); break;
-                case 4: PINT_EVAL_LAUNCH(0, 4); break;
-                case 5: PINT_EVAL_LAUNCH(0, 5); break;
-                case 6: PINT_EVAL_LAUNCH(0, 6); break;
-                case 7: PINT_EVAL_LAUNCH(0, 7); break;
-                case 8: PINT_EVAL_LAUNCH(0, 8); break;
-                case PINT_BLK_FB_ELL1: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_ELL1); break;
-                case PINT_BLK_FB_DD: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_DD); break;
-                case PINT_BLK_FB_ELL1H: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_ELL1H); break;
-                default: PINT_EVAL_LAUNCH(0, PINT_BLK_FB_BT); break;
-            }
+            kern = t == 1 ? k_eval<1, 1, 3> : k_eval<1, 2, 3>;
         }
-#undef PINT_EVAL_LAUNCH
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, bi, br, tabs, icp,
+                           ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, ctx->d_dmxv,
+                           want_M == 2 ? 1 : 0, write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs);
         HIPCHK(hipGetLastError());
     }
-    if (ctx->any_wavex) {  // WaveX / DMWaveX: the total delay, the phase at it and their columns (before k_glitch)
-        // (a batch with chromatic terms takes the chromatic build; every other batch the plain one)
-        auto kw = ctx->any_chrom ? k_wavex<true> : k_wavex<false>;
-        hipLaunchKernelGGL(kw, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
-                           want_M == 2 ? 1 : 0, ctx->d_status, ctx->d_istatus);
-        HIPCHK(hipGetLastError());
-    }
-    if (ctx->any_fdjump) {  // FDJump / FDJumpDM: their delays, the phase at the new total, their columns
-        hipLaunchKernelGGL(k_fdjump, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
-                           want_M == 2 ? 1 : 0, ctx->d_status, ctx->d_istatus);
-        HIPCHK(hipGetLastError());
-    }
-    if (ctx->any_glitch) {  // Glitch: the phase of every row and the glitch columns, on the evaluation's outputs
-        hipLaunchKernelGGL(k_glitch, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,
-                           want_M == 2 ? 1 : 0);
-        HIPCHK(hipGetLastError());
-    }
-    if (ctx->any_phase_terms) {  // PiecewiseSpindown / Wave / IFunc: their phases at the final delay, the piece columns
-        hipLaunchKernelGGL(k_phase_terms, dim3(ctx->ninst, (ctx->maxn + 256) / 256), dim3(256), 0, ctx->stream,
-                           ctx->d_psrs, ctx->d_inst, tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo,
-                           want_M ? ctx->d_M : nullptr, want_M == 2 ? 1 : 0);
-        HIPCHK(hipGetLastError());
-    }
+    // the passes after the evaluation, in their fixed order (the contract above k_sw_geom), each
+    // only for a batch that has its component: one launch on the rows' grid, the shared leading
+    // arguments, then the pass's own (the status words of the passes that bound the added delay)
+#define PINT_PASS(kern, ...)                                                                                       \
+    do {                                                                                                           \
+        hipLaunchKernelGGL(kern, pass_grid(ctx, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, \
+                           tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,         \
+                           want_M == 2, ##__VA_ARGS__);                                                            \
+        HIPCHK(hipGetLastError());                                                                                 \
+    } while (0)
+    // (a batch with chromatic terms takes the chromatic build; every other batch the plain one)
+    const auto kw = ctx->post & POST_CHROM ? k_wavex<true> : k_wavex<false>;
+    if (ctx->post & POST_WAVEX) PINT_PASS(kw, ctx->d_status, ctx->d_istatus);
+    if (ctx->post & POST_FDJUMP) PINT_PASS(k_fdjump, ctx->d_status, ctx->d_istatus);
+    if (ctx->post & POST_GLITCH) PINT_PASS(k_glitch);
+    if (ctx->post & POST_PHASE_TERMS) PINT_PASS(k_phase_terms);
+#undef PINT_PASS
     record(ctx, want_M ? 3 : 1);
     record(ctx, 4);
     if (ctx->nrblk > 0) {
