@@ -402,6 +402,17 @@ int pint_set_instances(pint_ctx *ctx, int ninst, const int32_t *inst_psr, const 
  * Otherwise as pint_set_instances. */
 int pint_set_grid(pint_ctx *ctx, int psr, int npts, const double *base, int nvar, const int32_t *var_toff,
                   const int64_t *var_stride, const int64_t *var_size, const double *vals, int64_t k0);
+/* npts instances of pulsar psr, each with its own value of any number of parameters (a sampler's
+ * walkers, a nested sampler's live points; BayesianTiming's batch): point k's table is `base`
+ * (tstride doubles) with the nvar (hi, lo) entries at table offsets var_toff[j] replaced by
+ * vals[2 (k nvar + j)], vals[2 (k nvar + j) + 1] -- point-major, npts x nvar pairs.  The tables are
+ * formed on the device (k_point_tables: one map lookup per entry, so nvar is bounded by the table
+ * alone, 2 nvar <= tstride; offsets must be distinct).  When the pulsar and the point count are
+ * those of the resident pint_set_grid / pint_set_points batch, only the tables change -- no host
+ * set-up, no instance upload (PINT_QUERY_NREUSE counts such calls).  Otherwise as
+ * pint_set_instances. */
+int pint_set_points(pint_ctx *ctx, int psr, int npts, const double *base, int nvar, const int32_t *var_toff,
+                    const double *vals);
 int pint_get_tables(pint_ctx *ctx, double *tables_out);
 int pint_set_tables(pint_ctx *ctx, const double *tables);
 
@@ -643,6 +654,8 @@ int pint_graph_launch(pint_ctx *ctx);
 #define PINT_QUERY_NSPINEVAL 3
 #define PINT_QUERY_WFUSE 4      /* 1: the batch's residual pass forms the post-fit Woodbury dots (k_resid2
                                    tiles): every noise basis a PLRedNoise series of at most 63 modes */
+#define PINT_QUERY_NREUSE 5     /* pint_set_grid / pint_set_points calls of this context that kept the resident
+                                   batch (same pulsar, point count and options) and only formed new tables */
 int pint_query(pint_ctx *ctx, int key);
 /* The launch plan of the last pint_fit_step (host bookkeeping, no reference counterpart): which
  * kernel instantiations the call enqueued, as the dispatcher chose them from the batch's padded
@@ -757,6 +770,38 @@ int pint_set_noise_classes(pint_ctx *ctx, int psr, int ncls, const int32_t *cls_
  * 2 EQUAD_p F_c^2 1e-12 cls_g[2c+1], dlnL/dECORR_p = sum_{e of p} 2 ECORR_p 1e-12 ep_g[e]. */
 int pint_noise_lnlike(pint_ctx *ctx, const int32_t *kind, const double *cls_qf, const double *ep_w, double *out3,
                       double *cls_g, double *ep_g);
+
+/* ---- posterior sampling (bayesian.py BayesianTiming) ---------------------------------------
+ * The white-noise log-likelihood of many points at once, every point with its own timing
+ * parameters (pint_set_points) and its own EFAC / EQUAD / DMEFAC / DMEQUAD values.
+ *
+ * pint_set_dm_noise_classes: the DM-side twin of pint_set_noise_classes for a pulsar with
+ * wideband DM data (after pint_set_wideband): its TOAs grouped by the set of DMEFAC / DMEQUAD
+ * masks that select them, CSR, with the raw -pp_dme errors dme0[n] (pc/cm^3).  A class's scaled DM
+ * error is sqrt(dme0_i^2 + Q^2) F, Q^2 the sum of its DMEQUAD^2, F the product of its DMEFACs
+ * (ScaleDmError.scale_dm_sigma, noise_model.py:291).
+ *
+ * pint_point_lnlike, after pint_eval(ctx, 0): for every instance k, with its own (Q^2 [us^2], F) per
+ * TOA class in cls_qf and (Q^2 [(pc/cm^3)^2], F) per DM class in dmcls_qf (the instances' classes
+ * concatenated; dmcls_qf NULL when no pulsar of the batch has wideband data),
+ *   out[5k]     lnL = -chi2_toa / 2 - sum log sigma_toa - chi2_dm / 2 - sum log sigma_dm
+ *               (bayesian.py:202-252 _wls_nb_lnlikelihood / _wls_wb_lnlikelihood),
+ *   out[5k + 1] chi2_toa, the time residuals over the point's scaled errors, the weighted mean
+ *               taken with the point's own errors (unless the model has a PhaseOffset),
+ *   out[5k + 2] sum_i log sigma_i, sigma in seconds,
+ *   out[5k + 3] chi2_dm of pp_dm - (DM series + DMX + DMJUMP + NE_SW), no mean removed,
+ *   out[5k + 4] sum_i log sigma_dm,i with sigma_dm in m^-2 (the reference takes the SI value of
+ *               the pc/cm^3 errors: log(3.0856775814913673e22) per TOA more than in pc/cm^3);
+ * the last two are 0 without wideband data.  ncls_tot / ndmcls_tot: the number of (Q^2, F) pairs
+ * in each array.  PINT_E_INVALID with a message, before any launch, when a pulsar of the batch has
+ * no classes (pint_set_noise_classes), has wideband data but no DM classes or dmcls_qf is NULL, or a
+ * count is not the batch's sum of classes.  Lazy mode: only enqueued (cls_qf, dmcls_qf and out must
+ * stay valid until pint_check), like pint_chi2_wls.  A zero or negative scaled error gives what
+ * IEEE arithmetic gives the reference's expressions (infinities and NaNs), never an error. */
+int pint_set_dm_noise_classes(pint_ctx *ctx, int psr, int ncls, const int32_t *cls_ptr, const int32_t *cls_idx,
+                              const double *dme0);
+int pint_point_lnlike(pint_ctx *ctx, int64_t ncls_tot, const double *cls_qf, int64_t ndmcls_tot,
+                      const double *dmcls_qf, double *out);
 
 #ifdef __cplusplus
 }

@@ -16,3 +16,12 @@ from .gridutils import grid_chisq, grid_chisq_derived, tuple_chisq, tuple_chisq_
 from .wavex import wavex_setup, dmwavex_setup, cmwavex_setup, get_wavex_freqs, get_wavex_amps  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # BayesianTiming (bayesian.py) and the priors need scipy.stats: imported at first use, so
+    # that `import pint_amd` stays as quick as it was
+    if name == "BayesianTiming":
+        from .bayesian import BayesianTiming
+        return BayesianTiming
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

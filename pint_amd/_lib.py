@@ -206,6 +206,9 @@ def lib():
     L.pint_set_noise_weights.argtypes = [vp, C.c_int, dptr, dptr]
     L.pint_set_noise_classes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dptr]
     L.pint_noise_lnlike.argtypes = [vp, C.POINTER(C.c_int32), dptr, dptr, dptr, dptr, dptr]
+    L.pint_set_points.argtypes = [vp, C.c_int, C.c_int, dptr, C.c_int, C.POINTER(C.c_int32), dptr]
+    L.pint_set_dm_noise_classes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dptr]
+    L.pint_point_lnlike.argtypes = [vp, C.c_int64, dptr, C.c_int64, dptr, dptr]
     _lib = L
     L.pint_set_wideband.argtypes = [vp, C.c_int, dptr, dptr, dptr, C.POINTER(C.c_uint64)]
     L.pint_dm_resids.argtypes = [vp, C.c_int, C.c_int, dptr, dptr]
@@ -224,7 +227,8 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_noise_lnlike", "pint_noise_resids_dm", "pint_set_wideband", "pint_dm_resids", "pint_chi2_wls",
             "pint_apply_step_uniform", "pint_fit_step_apply", "pint_save_tables", "pint_restore_tables", "pint_read_norms",
             "pint_fit_step_enqueue", "pint_set_grid", "pint_add_pulsar_cols", "pint_pack_toas",
-            "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms"]
+            "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms",
+            "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

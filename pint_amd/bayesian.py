@@ -1,0 +1,266 @@
+"""BayesianTiming (reference ``src/pint/bayesian.py``): the pulsar-timing log-likelihood, prior
+and posterior for posterior sampling (MCMC, nested sampling), evaluated in batches on the device.
+
+The reference evaluates one parameter vector per call by rebuilding a Residuals object.  A
+sampler wants many independent points per step, so every method here has a batch form that takes
+an ``(N, nparams)`` array and returns ``(N,)`` float64; the scalar forms are the batch forms at
+N = 1.  ``lnposterior_batch`` works directly as emcee's ``vectorize=True`` callable.
+
+One pulsar stays resident on the device (one Session per object).  A batch installs its N points
+as instances with pint_set_points (each point replaces the table entries of every free timing
+parameter; a batch of the same N as the last one only forms new tables), runs the evaluation and
+the residual pass as grid_chisq does, and then one likelihood pass (pint_point_lnlike) in which
+every point scales the TOA errors with its own EFAC / EQUAD (and the DM errors with its own
+DMEFAC / DMEQUAD), takes its own weighted mean, and forms
+
+    lnL = -chi2_toa / 2 - sum log sigma_i  [- chi2_dm / 2 - sum log sigma_dm,i  (wideband)]
+
+(bayesian.py:202-252).  Priors and the prior transform are column-wise scipy on the host.
+
+Differences from the reference, all of them documented in DESIGN.md section 4: a NaN log-prior
+counts as -inf (the reference's ``in (np.nan, -np.inf)`` test never matches a computed NaN);
+``lnposterior`` of a point the device cannot evaluate (e.g. ECC >= 1 under an allowing prior) is
+NaN instead of an exception; free parameters must have a slot in the device table or be
+EFAC / EQUAD / DMEFAC / DMEQUAD.  The correlated-noise (GLS) likelihood is refused as in the
+reference.
+"""
+from __future__ import annotations
+
+import copy
+from typing import Optional
+
+import numpy as np
+
+from . import _lib as L
+from .priors import Prior, UniformUnboundedRV
+
+LD = np.longdouble
+WHITE = ("EFAC", "EQUAD", "DMEFAC", "DMEQUAD")
+EVAL_ERRORS = (L.PINT_E_KEPLER, L.PINT_E_PARAM)
+
+
+def _base(name: str) -> str:
+    return name.rstrip("0123456789")
+
+
+def _is_unbounded(prior) -> bool:
+    rv = prior._rv
+    return isinstance(rv, UniformUnboundedRV) or isinstance(getattr(rv, "dist", None), UniformUnboundedRV)
+
+
+class BayesianTiming:
+    """lnprior, prior_transform, lnlikelihood and lnposterior of a timing model and TOAs.
+
+    model : the timing model; a deep copy is kept, its values are the base values of every batch.
+    toas : the TOAs (narrowband or wideband).
+    use_pulse_numbers : track pulse numbers instead of the nearest integer; TOAs without pulse
+        numbers get them from the initial model's phase (TOAs.compute_pulse_numbers).
+    prior_info : {name: {"distr": "uniform", "pmin": .., "pmax": ..} or {"distr": "normal",
+        "mu": .., "sigma": ..}}; supersedes the priors set on the model's parameters.
+    """
+
+    def __init__(self, model, toas, use_pulse_numbers=False, prior_info=None):
+        from scipy.stats import norm, uniform
+        self.model = copy.deepcopy(model)
+        self.toas = toas
+        if use_pulse_numbers:
+            pn = toas.get_pulse_numbers()
+            if pn is None or np.any(np.isnan(pn)):
+                toas.compute_pulse_numbers(self.model)
+        self.track_mode = "use_pulse_numbers" if use_pulse_numbers else "nearest"
+        self.is_wideband = toas.is_wideband()
+        self.param_labels = self.model.free_params
+        self.params = [self.model[p] for p in self.param_labels]
+        self.nparams = len(self.param_labels)
+        if prior_info is not None:
+            for par, info in prior_info.items():
+                distr = info["distr"]
+                if distr == "uniform":
+                    self.model[par].prior = Prior(uniform(info["pmin"], info["pmax"] - info["pmin"]))
+                elif distr == "normal":
+                    self.model[par].prior = Prior(norm(info["mu"], info["sigma"]))
+                else:
+                    raise NotImplementedError("Only uniform and normal distributions are supported in prior_info.")
+        self._validate_priors()
+        self.likelihood_method = self._decide_likelihood_method()
+        self._plan()
+        self._dev = None
+
+    # -- construction ------------------------------------------------------------------
+    def _validate_priors(self):
+        for p in self.params:
+            if _is_unbounded(p.prior):
+                raise NotImplementedError(f"Unbounded uniform priors are not supported. (param : {p.name})")
+
+    def _decide_likelihood_method(self):
+        if self.model.has_correlated_errors:
+            raise NotImplementedError("GLS likelihood for correlated noise is not yet implemented.")
+        return "wls"
+
+    def _plan(self):
+        """Host layout of the pulsar and the split of the free parameters into table entries
+        (timing parameters) and white-noise parameters; the white-noise classes."""
+        from .engine import build_layout
+        from .noisefit import white_noise_classes
+        m = self.model
+        self.lay = build_layout(m, self.toas, track_mode=self.track_mode, use_gls_basis=False)
+        self._timing = [(j, p) for j, p in enumerate(self.param_labels) if p in self.lay.offsets]
+        col = {p: j for j, p in enumerate(self.param_labels)}
+        for p in self.param_labels:
+            if p not in self.lay.offsets and not (m[p].kind == "mask" and _base(p) in WHITE):
+                raise NotImplementedError(f"free parameter {p} has no slot in the device table and is not a white-noise "
+                                          f"parameter (EFAC, EQUAD, DMEFAC, DMEQUAD): it cannot be sampled")
+        self._base_values = np.array([LD(0) if m[p].value is None else LD(m[p].value) for p in self.param_labels], dtype=LD)
+
+        def classes(efac, equad):
+            ptr, idx, cef, ceq = white_noise_classes(m, self.toas, efac, equad)
+            # per class: its EFACs and EQUADs as (column of the sample array, or -1 and the fixed value)
+            ref = lambda n: (col.get(n, -1), float(m[n].value))  # noqa: E731
+            return ptr, idx, [[ref(n) for n in c] for c in cef], [[ref(n) for n in c] for c in ceq]
+        self._cls = classes("EFAC", "EQUAD")
+        self._dmcls = classes("DMEFAC", "DMEQUAD") if self.is_wideband else None
+
+    def _device(self):
+        """The resident Session with the pulsar, its wideband data and its noise classes."""
+        if self._dev is None:
+            from .engine import Session, pack_table
+            s = Session()
+            try:
+                s.set_timing_mask(0)
+                lay = s.add(self.lay)
+                s.set_noise_classes(lay, self._cls[0], self._cls[1], self.toas.get_errors())
+                if self.is_wideband:
+                    s.set_wideband(lay)
+                    s.set_dm_noise_classes(lay, self._dmcls[0], self._dmcls[1], self.toas.get_dm_errors())
+                self._table0 = pack_table(lay, self.model)
+            except Exception:
+                s.close()
+                raise
+            self._dev = s
+        return self._dev
+
+    def close(self):
+        if getattr(self, "_dev", None) is not None:
+            self._dev.close()
+            self._dev = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- arguments ---------------------------------------------------------------------
+    def _points(self, params, batch):
+        v = np.asarray(params)
+        if v.dtype != LD:
+            v = v.astype(np.float64)
+        if not batch:
+            if v.ndim != 1 or len(v) != self.nparams:
+                raise IndexError(f"The number of input parameters ({len(params)}) should be the same "
+                                 f"as the number of free parameters ({self.nparams}).")
+            return v[None, :]
+        if v.ndim != 2 or v.shape[1] != self.nparams:
+            raise IndexError(f"The number of input parameters ({v.shape[-1] if v.ndim else 0}) should be the same "
+                             f"as the number of free parameters ({self.nparams}).")
+        return v
+
+    # -- prior -------------------------------------------------------------------------
+    def lnprior_batch(self, params):
+        """The factorised log-prior of every point, (N,); -inf where any parameter's is -inf or NaN."""
+        v = self._points(params, True)
+        total = np.zeros(v.shape[0])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for j, p in enumerate(self.params):
+                total = total + np.asarray(p.prior_pdf(np.ascontiguousarray(v[:, j]), logpdf=True), dtype=np.float64)
+        return np.where(np.isnan(total), -np.inf, total)
+
+    def lnprior(self, params):
+        return float(self.lnprior_batch(self._points(params, False))[0])
+
+    def prior_transform_batch(self, cube):
+        """Points of the unit hypercube mapped to the prior distribution, (N, nparams) float64."""
+        c = np.asarray(cube, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != self.nparams:
+            raise IndexError(f"The number of input parameters ({c.shape[-1] if c.ndim else 0}) should be the same "
+                             f"as the number of free parameters ({self.nparams}).")
+        return np.column_stack([np.asarray(p.prior.ppf(np.ascontiguousarray(c[:, j])), dtype=np.float64)
+                                for j, p in enumerate(self.params)]) if self.nparams else np.zeros_like(c)
+
+    def prior_transform(self, cube):
+        return self.prior_transform_batch(np.asarray(cube, dtype=np.float64)[None, :])[0]
+
+    # -- likelihood --------------------------------------------------------------------
+    @staticmethod
+    def _qf(v, cls):
+        """(N, ncls, 2): Q^2 = the sum of the class's EQUAD^2, F = the product of its EFACs, per point."""
+        _, _, cef, ceq = cls
+        out = np.empty((v.shape[0], len(cef), 2))
+        val = lambda r: np.asarray(v[:, r[0]], dtype=np.float64) if r[0] >= 0 else r[1]  # noqa: E731
+        for c in range(len(cef)):
+            q2 = np.zeros(v.shape[0])
+            for r in ceq[c]:
+                q2 = q2 + val(r) ** 2
+            f = np.ones(v.shape[0])
+            for r in cef[c]:
+                f = f * val(r)
+            out[:, c, 0], out[:, c, 1] = q2, f
+        return out
+
+    def _chunk(self, n):
+        from .gridutils import GRID_BATCH_BYTES
+        lay = self.lay
+        per_pt = 8.0 * (lay.n * (lay.K + 12) + 64 * (lay.K + 2) ** 2)
+        return int(max(1, min(n, GRID_BATCH_BYTES // per_pt)))
+
+    def lnlikelihood_terms_batch(self, params):
+        """(N, 5): lnL, chi2_toa, sum log sigma_toa (s), chi2_dm, sum log sigma_dm (SI, as the
+        reference takes it) of every point; a point the device flags (pint_inst_status) is NaN."""
+        v = self._points(params, True)
+        s = self._device()
+        lay = self.lay
+        out = np.empty((v.shape[0], 5))
+        names = [p for _, p in self._timing]
+        cols = [j for j, _ in self._timing]
+        chunk = self._chunk(v.shape[0])
+        for c0 in range(0, v.shape[0], chunk):
+            vc = v[c0:c0 + chunk]
+            s.set_points(lay, self._table0, names, vc[:, cols])
+            flagged = False
+            try:
+                s.eval(False)
+            except L.PintError as e:
+                if e.code not in EVAL_ERRORS:
+                    raise
+                flagged = True
+            got = s.point_lnlike(self._qf(vc, self._cls), self._qf(vc, self._dmcls) if self.is_wideband else None)
+            got = np.array(got, dtype=np.float64)
+            if flagged:
+                got[s.inst_status() != 0] = np.nan
+            out[c0:c0 + chunk] = got
+        return out
+
+    def lnlikelihood_batch(self, params):
+        """The log-likelihood of every point, (N,) (bayesian.py:163-187 at each row)."""
+        return self.lnlikelihood_terms_batch(params)[:, 0].copy()
+
+    def lnlikelihood(self, params):
+        return float(self.lnlikelihood_batch(self._points(params, False))[0])
+
+    def lnposterior_batch(self, params):
+        """lnprior + lnlikelihood of every point, (N,): -inf where the prior is not finite (such a
+        point runs at the base values in the batch, so nothing invalid is evaluated on its
+        account), NaN where the prior is finite and the device flags the point."""
+        v = self._points(params, True)
+        lp = self.lnprior_batch(v)
+        ok = np.isfinite(lp)
+        if not ok.all():
+            v = v.copy()
+            v[~ok] = self._base_values.astype(v.dtype)
+        with np.errstate(invalid="ignore"):
+            return np.where(ok, lp + self.lnlikelihood_batch(v), -np.inf)
+
+    def lnposterior(self, params):
+        return float(self.lnposterior_batch(self._points(params, False))[0])
+
+    __call__ = lnposterior_batch

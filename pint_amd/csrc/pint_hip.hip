@@ -129,6 +129,11 @@ struct PsrDev {
     // per term) and count; IFunc's type, count and control points (x as hi and lo, y)
     int o_pw, npw, o_wave, nwave, sifunc, nifunc;
     const double *ifx_hi, *ifx_lo, *ify;
+    // DM-error classes (pint_set_dm_noise_classes): the DMEFAC / DMEQUAD twin of toa_cls / sigma0 --
+    // each TOA's class and its raw -pp_dme error (pc/cm^3)
+    const int32_t* dm_cls;
+    const double* dme0;
+    int ndmcls;
 };
 
 struct InstDev {
@@ -5781,6 +5786,96 @@ __global__ __launch_bounds__(256) void k_noise_lnl(const PsrDev* __restrict__ ps
     }
 }
 
+// k_point_lnl: the white-noise log-likelihood of every instance at its own EFAC / EQUAD (and
+// DMEFAC / DMEQUAD) values, after the residual pass (BayesianTiming._wls_nb_lnlikelihood /
+// _wls_wb_lnlikelihood, bayesian.py:202-252): lnL = -chi2_toa / 2 - sum log sigma_i - chi2_dm / 2 -
+// sum log sigma_dm,i with sigma_i = sqrt(sigma0_i^2 + Q_c^2) F_c (us -> s) of the TOA's class c
+// (noise_model.py:159: EQUADs in quadrature, then EFACs).  The residual pass subtracted the mean
+// weighted by the pulsar's sigma; the point's own weighted mean (residuals.py:314-425) is a
+// correction to its output, exactly: p'_i = p_i - sum w' p / sum w' on the phase residuals
+// (p_i = full_i - m0, so p'_i = full_i - sum w' full / sum w'), then the division by the row's
+// ftay (calc_time_resids).  No correction without mean subtraction (PhaseOffset) or with the
+// unweighted mean.  The DM rows are wb_row's (the modelled DM of k_dm_resid / k_wb_gram), no mean
+// removed, sigma_dm = sqrt(dme0^2 + Q^2) F of the TOA's DM class (noise_model.py:291); their log sum
+// is of sigma_dm in SI units as the reference takes it (dm_lnunit = log(pc cm^-3 / m^-2) per row).
+// NW waves per instance (NW == 1: a wave per instance, four instances per workgroup, no workgroup
+// barrier); every sum a thread's strided partial, then block_sums' fixed order: the same bits on
+// every run.  qoff: per instance the first TOA class and DM class of its values (null: instance k
+// of one pulsar starts at k ncls, k ndmcls).  Reads 28 B per TOA row (p, ftay, sigma0, class) twice
+// (the second pass from L2) and ~48 B per DM row.
+constexpr int PL_SMALLN = 512;   // rows up to which an instance takes one wave
+constexpr int PL_LARGEN = 4096;  // rows beyond which it takes 8 waves instead of 4
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? 256 : NW * 64) void k_point_lnl(
+    const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts, int ninst, const double* __restrict__ tables,
+    const InstConst* __restrict__ ic, const double* __restrict__ rphase, const double* __restrict__ ftay,
+    const double* __restrict__ qf, const double* __restrict__ dqf, const long* __restrict__ qoff, double dm_lnunit,
+    double* __restrict__ out) {
+    constexpr int BT = NW * 64;
+    __shared__ double sh[2 * NW];
+    const int k = NW == 1 ? blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)blockIdx.x;
+    if (NW == 1 && k >= ninst) return;  // (wave-uniform)
+    const int tid = threadIdx.x % BT;
+    const InstDev I = insts[k];
+    const PsrDev& Pd = psrs[I.psr];
+    const pint_spec_t& S = *Pd.spec;
+    const int n = I.n;
+    const double* p = rphase + I.ooff;
+    const double* f = ftay + I.roff;
+    const double* Q = qf + 2 * (qoff ? qoff[2 * k] : (long)k * Pd.ncls);
+    double mean = 0.0;
+    if (S.subtract_mean && S.weighted_mean) {
+        double v[2] = {0.0, 0.0};
+        for (int i = tid; i < n; i += BT) {
+            const int c = Pd.toa_cls[i];
+            const double s0 = Pd.sigma0[i], fc = Q[2 * c + 1];
+            const double w = 1.0 / ((s0 * s0 + Q[2 * c]) * (fc * fc));
+            v[0] += w * p[i];
+            v[1] += w;
+        }
+        block_sums<NW, 2>(v, sh);
+        mean = v[0] / v[1];
+    }
+    double t[2] = {0.0, 0.0};
+    for (int i = tid; i < n; i += BT) {
+        const int c = Pd.toa_cls[i];
+        const double s0 = Pd.sigma0[i];
+        const double sig = sqrt(s0 * s0 + Q[2 * c]) * Q[2 * c + 1] * 1e-6;
+        const double rt = (p[i] - mean) / f[i];
+        const double z = rt / sig;
+        t[0] += z * z;
+        t[1] += log(sig);
+    }
+    block_sums<NW, 2>(t, sh);
+    double d[2] = {0.0, 0.0};
+    if (Pd.wb) {  // (uniform over the instance's threads)
+        const double* D = dqf + 2 * (qoff ? qoff[2 * k + 1] : (long)k * Pd.ndmcls);
+        const double* P = tables + I.toff;
+        bool any = false;
+        for (int j = 1; j < S.ndm; j++) any |= (pval(P, S.o_DM + 2 * j) != 0.0);
+        const dd ep = S.o_DMEPOCH >= 0 ? pdd(P, S.o_DMEPOCH) : dd_make(0.0);
+        for (int i = tid; i < n; i += BT) {
+            double r, w, dtyr, swg;
+            wb_row(Pd, S, P, ic[k], i, any, ep, r, w, dtyr, swg);
+            const int c = Pd.dm_cls[i];
+            const double e0 = Pd.dme0[i];
+            const double sig = sqrt(e0 * e0 + D[2 * c]) * D[2 * c + 1];
+            const double z = r / sig;
+            d[0] += z * z;
+            d[1] += log(sig) + dm_lnunit;
+        }
+        block_sums<NW, 2>(d, sh);
+    }
+    if (tid == 0) {
+        double* o = out + 5 * (long)k;
+        o[0] = -0.5 * t[0] - t[1] - 0.5 * d[0] - d[1];
+        o[1] = t[0];
+        o[2] = t[1];
+        o[3] = d[0];
+        o[4] = d[1];
+    }
+}
+
 // Debug/parity introspection (pint_debug_gram): the assembled, unnormalised normal matrix
 // [M | r]^T N^-1 [M | r] of the last pint_fit_step in the original column order (the ECORR
 // block already eliminated by its Schur complement), (K+1)^2 per instance, followed by the K
@@ -6156,6 +6251,9 @@ struct pint_ctx {
     float ms[NMS] = {0, 0, 0, 0, 0, 0, 0, 0};
     double* d_nz = nullptr;  // pint_noise_lnlike scratch (parameters, epoch sums, outputs)
     size_t nz_cap = 0;
+    double* d_pl = nullptr;  // pint_point_lnlike scratch (class parameters, offsets, outputs)
+    size_t pl_cap = 0;
+    int n_batch_reuse = 0;   // pint_set_grid / pint_set_points calls that kept the resident batch (PINT_QUERY_NREUSE)
     double* d_noise = nullptr;  // pint_noise_resids: red and ECORR realisations (2 tot_out)
     long noise_cap = 0;
     double* d_tables0 = nullptr;  // pint_save_tables snapshot
@@ -6588,6 +6686,23 @@ __global__ __launch_bounds__(256) void k_grid_tables(const double* __restrict__ 
     }
 }
 
+// pint_set_points: tables[k] = base with point k's own (hi, lo) pairs set.  spec: the base table
+// (ts), then per table slot the index into a point's values of the entry that replaces it (2 j + (0
+// hi, 1 lo) for variable j, -1: the base value; as doubles, exact), then the points' values, 2 nvar
+// per point.  One load of the map and one of the value per entry, whatever nvar is.
+__global__ __launch_bounds__(256) void k_point_tables(const double* __restrict__ spec, int ts, int nvar, int npts,
+                                                      double* __restrict__ tables) {
+    const long total = (long)npts * ts;
+    const double* map = spec + ts;
+    const double* vals = map + ts;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const long k = e / ts;
+        const int i = (int)(e - k * ts);
+        const int m = (int)map[i];
+        tables[e] = m < 0 ? spec[i] : vals[k * 2 * nvar + m];
+    }
+}
+
 static int refresh_psrs(pint_ctx* ctx) {
     if (int rc = commit_uploads(ctx)) return rc;
     ctx->psrs_dirty = false;
@@ -6778,6 +6893,7 @@ void pint_ctx_destroy(pint_ctx* ctx) {
     if (ctx->d_dmr) hipFree(ctx->d_dmr);
     if (ctx->d_dmc2) hipFree(ctx->d_dmc2);
     if (ctx->d_nz) hipFree(ctx->d_nz);
+    if (ctx->d_pl) hipFree(ctx->d_pl);
     if (ctx->d_status_slots) hipFree(ctx->d_status_slots);
     if (ctx->h_status) hipHostFree(ctx->h_status);
     for (int sl = 0; sl < pint_ctx::NSLOT; sl++) {
@@ -7424,20 +7540,9 @@ int pint_set_instances(pint_ctx* ctx, int ninst, const int32_t* inst_psr, const 
 // pairs concatenated, size[j] pairs each) -- a meshgrid's axes, or every point's own value
 // (stride 1, size npts).
 static int flush_chi2(pint_ctx* ctx);
-int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar, const int32_t* var_toff,
-                  const int64_t* var_stride, const int64_t* var_size, const double* vals, int64_t k0) {
-    if (!ctx || npts <= 0 || !base || nvar < 0 || nvar > 16 || (nvar && (!var_toff || !var_stride || !var_size || !vals)))
-        return PINT_E_INVALID;
-    if (psr < 0 || psr >= (int)ctx->psrs.size()) { ctx->err = "bad pulsar id"; return PINT_E_INVALID; }
-    const int ts = ctx->psrs[psr].spec.tstride;
-    long nv = 0;
-    for (int j = 0; j < nvar; j++) {
-        if (var_toff[j] < 0 || var_toff[j] + 1 >= ts || var_stride[j] < 1 || var_size[j] < 1) {
-            ctx->err = "pint_set_grid: bad grid variable (table offset, stride or size)";
-            return PINT_E_INVALID;
-        }
-        nv += var_size[j];
-    }
+// The batch of pint_set_grid / pint_set_points: npts instances of pulsar psr, their tables still
+// to be formed by the caller's kernel.
+static int grid_batch(pint_ctx* ctx, int psr, int npts) {
     // the same pulsar and point count as the resident batch (the next grid over the same
     // TOAs, or the next chunk of one): every instance array, launch group and buffer is the
     // same, only the tables differ -- reset the batch's state as a fresh batch has it and
@@ -7465,6 +7570,7 @@ int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar
         }
         HIPCHK(hipMemsetAsync(ctx->d_istatus, 0, sizeof(int) * ctx->ninst, ctx->stream));
         HIPCHK(hipMemsetAsync(ctx->d_cov, 0, sizeof(double) * std::max<long>(1, ctx->tot_cv), ctx->stream));
+        ctx->n_batch_reuse++;
     } else {
         std::vector<int32_t> ip(npts, psr);
         if (int rc = set_instances_impl(ctx, npts, ip.data(), nullptr)) return rc;
@@ -7472,6 +7578,24 @@ int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar
         ctx->grid_psr = psr;
         ctx->grid_opts = gkey;
     }
+    return PINT_OK;
+}
+
+int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar, const int32_t* var_toff,
+                  const int64_t* var_stride, const int64_t* var_size, const double* vals, int64_t k0) {
+    if (!ctx || npts <= 0 || !base || nvar < 0 || nvar > 16 || (nvar && (!var_toff || !var_stride || !var_size || !vals)))
+        return PINT_E_INVALID;
+    if (psr < 0 || psr >= (int)ctx->psrs.size()) { ctx->err = "bad pulsar id"; return PINT_E_INVALID; }
+    const int ts = ctx->psrs[psr].spec.tstride;
+    long nv = 0;
+    for (int j = 0; j < nvar; j++) {
+        if (var_toff[j] < 0 || var_toff[j] + 1 >= ts || var_stride[j] < 1 || var_size[j] < 1) {
+            ctx->err = "pint_set_grid: bad grid variable (table offset, stride or size)";
+            return PINT_E_INVALID;
+        }
+        nv += var_size[j];
+    }
+    if (int rc = grid_batch(ctx, psr, npts)) return rc;
     // the spec: base table, then per variable (toff, stride, size, value offset) as doubles
     // (exact: all < 2^53), then the value pairs
     // (the spec stays in the context until the next pint_set_grid, which synchronises the
@@ -7515,6 +7639,48 @@ int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar
         }
         ctx->tables_fresh = true;
     }
+    if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+// npts points of one pulsar, each replacing any number of table entries (a sampler's walkers, a
+// nested sampler's live points): pint_set_grid's batch -- the same reuse of the resident one -- with
+// the tables formed by k_point_tables from the base table, a slot map and the points' values.
+int pint_set_points(pint_ctx* ctx, int psr, int npts, const double* base, int nvar, const int32_t* var_toff,
+                    const double* vals) {
+    if (!ctx || npts <= 0 || !base || nvar < 0 || (nvar && (!var_toff || !vals))) return PINT_E_INVALID;
+    if (psr < 0 || psr >= (int)ctx->psrs.size()) { ctx->err = "bad pulsar id"; return PINT_E_INVALID; }
+    const int ts = ctx->psrs[psr].spec.tstride;
+    if (2 * nvar > ts) { ctx->err = "pint_set_points: more variables than table entries"; return PINT_E_INVALID; }
+    std::vector<double> map((size_t)ts, -1.0);
+    for (int j = 0; j < nvar; j++) {
+        const int o = var_toff[j];
+        if (o < 0 || o + 1 >= ts || map[o] >= 0.0 || map[o + 1] >= 0.0) {
+            ctx->err = "pint_set_points: bad variable (table offset outside the table, or entries named twice)";
+            return PINT_E_INVALID;
+        }
+        map[o] = 2.0 * j;
+        map[o + 1] = 2.0 * j + 1.0;
+    }
+    if (int rc = grid_batch(ctx, psr, npts)) return rc;
+    // (the spec stays in the context until the next call, which synchronises the streams first)
+    std::vector<double>& spec = ctx->grid_spec_host;
+    const size_t nval = (size_t)2 * nvar * npts;
+    spec.resize((size_t)2 * ts + nval);
+    for (int i = 0; i < ts; i++) {
+        spec[i] = base[i];
+        spec[ts + i] = map[i];
+    }
+    if (nval) memcpy(spec.data() + 2 * ts, vals, sizeof(double) * nval);
+    dfree((void*&)ctx->d_gridspec);  // (the previous batch's: its tables were formed, the streams synchronised)
+    HIPCHK(cmalloc((void**)&ctx->d_gridspec, sizeof(double) * spec.size()));
+    HIPCHK(h2d(ctx->d_gridspec, spec.data(), sizeof(double) * spec.size(), ctx->stream, false));
+    const long total = (long)npts * ts;
+    const int nb = (int)std::min<long>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(k_point_tables, dim3(nb), dim3(256), 0, ctx->stream, ctx->d_gridspec, ts, nvar, npts, ctx->d_tables);
+    HIPCHK(hipGetLastError());
+    ctx->spin_grid = 0;
+    ctx->tables_fresh = false;
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }
@@ -9305,6 +9471,7 @@ int pint_query(pint_ctx* ctx, int key) {
     if (key == PINT_QUERY_NSPLIT) return ctx->nsplit;
     if (key == PINT_QUERY_NSPINEVAL) return ctx->n_spin_eval;
     if (key == PINT_QUERY_WFUSE) return ctx->wfuse ? 1 : 0;
+    if (key == PINT_QUERY_NREUSE) return ctx->n_batch_reuse;
     ctx->err = "unknown query";
     return -PINT_E_INVALID;
 }
@@ -9837,6 +10004,112 @@ int pint_noise_lnlike(pint_ctx* ctx, const int32_t* kind, const double* cls_qf, 
     if (ep_g && ctx->tot_ep > 0)
         HIPCHK(d2h(ep_g, d_eg, sizeof(double) * ctx->tot_ep, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+// The DM-error classes of pulsar psr: pint_set_noise_classes' twin for DMEFAC / DMEQUAD.
+int pint_set_dm_noise_classes(pint_ctx* ctx, int psr, int ncls, const int32_t* cls_ptr, const int32_t* cls_idx,
+                              const double* dme0) {
+    if (!ctx || psr < 0 || psr >= (int)ctx->psrs.size() || ncls <= 0 || !cls_ptr || !cls_idx || !dme0)
+        return PINT_E_INVALID;
+    hipSetDevice(ctx->device);
+    if (int rc_ = commit_uploads(ctx)) return rc_;  // (staged pulsar uploads first)
+    PsrHost& ph = ctx->psrs[psr];
+    const int n = ph.n;
+    if (!ph.dev.wb) { ctx->err = "pint_set_dm_noise_classes: the pulsar has no wideband DM data (pint_set_wideband)"; return PINT_E_INVALID; }
+    if (cls_ptr[0] != 0 || cls_ptr[ncls] != n) { ctx->err = "DM noise classes must cover every TOA once"; return PINT_E_INVALID; }
+    std::vector<int32_t> tc(n, -1);
+    for (int c = 0; c < ncls; c++) {
+        if (cls_ptr[c + 1] < cls_ptr[c]) { ctx->err = "bad DM noise class list"; return PINT_E_INVALID; }
+        for (int k = cls_ptr[c]; k < cls_ptr[c + 1]; k++) {
+            const int i = cls_idx[k];
+            if (i < 0 || i >= n || tc[i] >= 0) { ctx->err = "DM noise classes must cover every TOA once"; return PINT_E_INVALID; }
+            tc[i] = c;
+        }
+    }
+    for (int i = 0; i < n; i++)
+        if (!(dme0[i] > 0.0)) { ctx->err = "DM uncertainty must be > 0"; return PINT_E_INVALID; }
+    int rc = 0;
+    rc |= upload(ctx, ph, tc.data(), (size_t)n, ph.dev.dm_cls);
+    rc |= upload(ctx, ph, dme0, (size_t)n, ph.dev.dme0);
+    if (rc) return PINT_E_HIP;
+    ph.dev.ndmcls = ncls;
+    return refresh_psrs(ctx) ? PINT_E_HIP : PINT_OK;
+}
+
+// log(1 pc cm^-3 in m^-2): the reference's log of the scaled DM errors is of their SI value
+// (bayesian.py:249 `.si.value`), a constant per DM row
+static const double PL_DM_LNUNIT = std::log(3.0856775814913673e22);
+
+int pint_point_lnlike(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf, int64_t ndmcls_tot, const double* dmcls_qf,
+                      double* out) {
+    if (!ctx || ctx->ninst <= 0 || !cls_qf || !out) return PINT_E_INVALID;
+    const int ni = ctx->ninst;
+    // every check before any launch
+    long nq = 0, ndq = 0;
+    bool any_wb = false;
+    const bool one = ctx->upsr.size() == 1;
+    std::vector<long> qoff;
+    if (!one) qoff.resize(2 * (size_t)ni);
+    for (int k = 0; k < (one ? 1 : ni); k++) {
+        const PsrDev& d = ctx->psrs[ctx->inst[k].psr].dev;
+        if (d.ncls <= 0) { ctx->err = "pint_point_lnlike: no noise classes (pint_set_noise_classes)"; return PINT_E_INVALID; }
+        if (d.wb && d.ndmcls <= 0) {
+            ctx->err = "pint_point_lnlike: wideband DM data without DM noise classes (pint_set_dm_noise_classes)";
+            return PINT_E_INVALID;
+        }
+        any_wb = any_wb || d.wb;
+        if (one) {
+            nq = (long)ni * d.ncls;
+            ndq = d.wb ? (long)ni * d.ndmcls : 0;
+        } else {
+            qoff[2 * k] = nq;
+            qoff[2 * k + 1] = ndq;
+            nq += d.ncls;
+            ndq += d.wb ? d.ndmcls : 0;
+        }
+    }
+    if (any_wb && !dmcls_qf) { ctx->err = "pint_point_lnlike: wideband DM data without DM class values"; return PINT_E_INVALID; }
+    if (ncls_tot != nq || (any_wb && ndmcls_tot != ndq)) {
+        ctx->err = "pint_point_lnlike: class count does not match the batch (" + std::to_string(ncls_tot) + " / " +
+                   std::to_string(nq) + " TOA classes, " + std::to_string(ndmcls_tot) + " / " + std::to_string(ndq) +
+                   " DM classes)";
+        return PINT_E_INVALID;
+    }
+    flush_r2(ctx);
+    hipSetDevice(ctx->device);
+    // scratch: qf 2 nq | dqf 2 ndq | out 5 ni | qoff 2 ni (as doubles' storage)
+    const size_t need = (size_t)2 * nq + 2 * ndq + 5 * ni + 2 * ni;
+    if (need > ctx->pl_cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a lazy call's kernel may still read the old one)
+        if (ctx->d_pl) hipFree(ctx->d_pl);
+        ctx->d_pl = nullptr;
+        ctx->pl_cap = 0;
+        HIPCHK(hipMalloc(&ctx->d_pl, sizeof(double) * need));
+        ctx->pl_cap = need;
+    }
+    double* d_q = ctx->d_pl;
+    double* d_dq = d_q + 2 * nq;
+    double* d_out = d_dq + 2 * ndq;
+    long* d_qoff = (long*)(d_out + 5 * ni);
+    static_assert(sizeof(long) == sizeof(double), "offset packing");
+    HIPCHK(h2d(d_q, cls_qf, sizeof(double) * 2 * nq, ctx->stream, false));
+    if (any_wb) HIPCHK(h2d(d_dq, dmcls_qf, sizeof(double) * 2 * ndq, ctx->stream, false));
+    if (!one) HIPCHK(h2d(d_qoff, qoff.data(), sizeof(long) * qoff.size(), ctx->stream, true));
+    if (any_wb)
+        if (int rc = ensure_ic_solar_wind(ctx)) return rc;
+    const long* qo = one ? nullptr : d_qoff;
+#define PINT_PL_ARGS ctx->d_psrs, ctx->d_inst, ni, ctx->d_tables, ctx->d_ic, ctx->d_rp, ctx->d_ftay, d_q, d_dq, qo, PL_DM_LNUNIT, d_out
+    if (ctx->maxn <= PL_SMALLN)
+        hipLaunchKernelGGL(k_point_lnl<1>, dim3((ni + 3) / 4), dim3(256), 0, ctx->stream, PINT_PL_ARGS);
+    else if (ctx->maxn <= PL_LARGEN)
+        hipLaunchKernelGGL(k_point_lnl<4>, dim3(ni), dim3(256), 0, ctx->stream, PINT_PL_ARGS);
+    else  // (8 waves, not 16: a 1024-thread workgroup's 128 VGPRs per lane made the DM rows spill)
+        hipLaunchKernelGGL(k_point_lnl<8>, dim3(ni), dim3(512), 0, ctx->stream, PINT_PL_ARGS);
+#undef PINT_PL_ARGS
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(out, d_out, sizeof(double) * 5 * ni, ctx->stream));
+    if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }
 

@@ -866,6 +866,34 @@ class Session:
                                          L.ptr(vals), int(k0)))
         self._after_set([lay] * int(npts), int(npts) * lay.tstride, uniform=True)
 
+    def set_points(self, lay: PulsarLayout, base_table: np.ndarray, names, values):
+        """Points of one pulsar as instances (pint_set_points): point k's table is base_table with
+        the entries of the parameters `names` replaced by values[k] (an (npts, len(names)) array,
+        float64 or longdouble; each value becomes its (hi, lo) pair).  Any number of parameters;
+        a call with the resident batch's pulsar and point count only forms new tables."""
+        base = np.ascontiguousarray(base_table, dtype=np.float64)
+        if base.shape != (lay.tstride,):
+            raise ValueError(f"base table must have {lay.tstride} entries, got {base.shape}")
+        v = np.asarray(values)
+        if v.dtype != np.longdouble:
+            v = v.astype(np.float64)
+        if v.ndim != 2 or v.shape[1] != len(names):
+            raise ValueError(f"values must be (npts, {len(names)}), got {v.shape}")
+        npts = v.shape[0]
+        pairs = np.empty((npts, len(names), 2))
+        pairs[:, :, 0] = v  # (a longdouble rounds to its nearest double: split_ld's hi)
+        pairs[:, :, 1] = (v - pairs[:, :, 0].astype(v.dtype)) if v.dtype == np.longdouble else 0.0
+        toff = np.array([lay.offsets[p] for p in names], dtype=np.int32)
+        self._check(self.L.pint_set_points(self.ctx, lay.psr_id, int(npts), L.ptr(base), len(names),
+                                           L.ptr(toff, C.c_int32), L.ptr(pairs)))
+        if self.lazy:
+            self._keep.append(pairs)
+        self._after_set([lay] * int(npts), int(npts) * lay.tstride, uniform=True)
+
+    def n_batch_reuse(self):
+        """pint_set_grid / pint_set_points calls that kept the resident batch (PINT_QUERY_NREUSE)."""
+        return int(self.L.pint_query(self.ctx, 5))
+
     def _set(self, ids, tabs, lays, uniform=False):
         self._check(self.L.pint_set_instances(self.ctx, len(ids), L.ptr(ids, C.c_int32), L.ptr(tabs)))
         self._after_set(lays, len(tabs), uniform)
@@ -1409,6 +1437,29 @@ class Session:
         self._check(self.L.pint_noise_lnlike(self.ctx, L.ptr(kd, C.c_int32), L.ptr(q), L.ptr(w), L.ptr(out),
                                              L.ptr(g), L.ptr(eg)))
         return out.reshape(-1, 3), (g.reshape(-1, 2) if grad else None), (eg[:nep] if grad else None)
+
+    def set_dm_noise_classes(self, lay, cls_ptr, cls_idx, dme0):
+        """The pulsar's DM-error classes (pint_set_dm_noise_classes), after set_wideband."""
+        cp = np.ascontiguousarray(cls_ptr, dtype=np.int32)
+        ci = np.ascontiguousarray(cls_idx, dtype=np.int32)
+        e0 = np.ascontiguousarray(dme0, dtype=np.float64)
+        self._check(self.L.pint_set_dm_noise_classes(self.ctx, lay.psr_id, len(cp) - 1, L.ptr(cp, C.c_int32),
+                                                     L.ptr(ci, C.c_int32), L.ptr(e0)))
+
+    def point_lnlike(self, cls_qf, dmcls_qf=None):
+        """k_point_lnl over the batch, after eval(False): out [ninst, 5] = (lnL, chi2_toa, sum log
+        sigma_toa, chi2_dm, sum log sigma_dm) -- see include/pint_amd.h pint_point_lnlike.  cls_qf:
+        (Q^2, F) per TOA class and instance, dmcls_qf the same per DM class (None: no wideband
+        data).  Lazy: a pinned buffer, complete after check()."""
+        q = np.ascontiguousarray(cls_qf, dtype=np.float64).reshape(-1)
+        dq = None if dmcls_qf is None else np.ascontiguousarray(dmcls_qf, dtype=np.float64).reshape(-1)
+        ni = len(self.inst_layout)
+        out = self._pin("ptlnl", 5 * ni) if self.lazy else np.empty(5 * ni)
+        self._check(self.L.pint_point_lnlike(self.ctx, q.size // 2, L.ptr(q), 0 if dq is None else dq.size // 2,
+                                             L.ptr(dq), L.ptr(out)))
+        if self.lazy:
+            self._keep += [q, dq]
+        return out.reshape(ni, 5)
 
     def debug_set_resids(self, resids):
         """Replace every instance's time residuals (list of n-arrays, seconds)."""

@@ -73,12 +73,13 @@ def likelihood_kind(model) -> int:
     return KIND_ECORR_OFFSET
 
 
-def white_noise_classes(model, toas):
+def white_noise_classes(model, toas, efac="EFAC", equad="EQUAD"):
     """TOAs grouped by the EFAC/EQUAD masks that select them (first-appearance order):
-    (cls_ptr, cls_idx, efac_of_class, equad_of_class)."""
+    (cls_ptr, cls_idx, efac_of_class, equad_of_class).  efac / equad: the mask parameters' base
+    names (DMEFAC / DMEQUAD for the DM-error classes)."""
     n = toas.ntoas
-    efacs = model.mask_params("EFAC")
-    equads = [e for e in model.mask_params("EQUAD") if model[e].value is not None]
+    efacs = model.mask_params(efac)
+    equads = [e for e in model.mask_params(equad) if model[e].value is not None]
     names = efacs + equads
     bits = np.zeros((n, max(len(names), 1)), dtype=bool)
     for j, name in enumerate(names):

@@ -133,6 +133,30 @@ class Param:
     def uncertainty(self, v):
         self.uncertainty_value = None if v is None else float(v)
 
+    # -- prior (parameter.py:376-406) --------------------------------------------------
+    @property
+    def prior(self):
+        """The parameter's prior, a :class:`pint_amd.priors.Prior`; an unbounded uniform one
+        (no prior) until one is set."""
+        p = self.__dict__.get("_prior")
+        if p is None:
+            from .priors import Prior, UniformUnboundedRV
+            p = self.__dict__["_prior"] = Prior(UniformUnboundedRV())
+        return p
+
+    @prior.setter
+    def prior(self, p):
+        from .priors import Prior
+        if not isinstance(p, Prior):
+            raise ValueError("prior must be an instance of Prior()")
+        self.__dict__["_prior"] = p
+
+    def prior_pdf(self, value=None, logpdf=False):
+        """The prior density (or its log) at `value`, a plain number or array in the parameter's
+        unit; at the parameter's own value when none is given."""
+        value = self.value if value is None else value
+        return self.prior.logpdf(value) if logpdf else self.prior.pdf(value)
+
     def __repr__(self):
         return f"{self.name} ({self.units}) {self.value} frozen={self.frozen}"
 

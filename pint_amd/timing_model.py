@@ -228,6 +228,17 @@ class TimingModel:
         if want:
             raise ValueError(f"Parameter(s) not in the model: {sorted(want)}")
 
+    def set_param_values(self, fitp):
+        """Set the values of the named parameters (timing_model.py set_param_values): {name: value}.
+        Long-double and MJD parameters keep a longdouble (a float lands in it exactly), the others a
+        float, as the par-file parser leaves them."""
+        for name, v in fitp.items():
+            p = self._params[name]
+            if p.kind in ("float", "mjd", "hourangle", "degangle", "mask"):
+                p.value = LD(v) if (p.long_double or p.kind == "mjd") else float(v)
+            else:
+                p.value = v
+
     def get_params_dict(self, which="free", kind="value"):
         names = self.free_params if which == "free" else self.params
         return OrderedDict((n, self._params[n].value) for n in names)

@@ -172,6 +172,15 @@ class TOAs:
     def get_pulse_numbers(self) -> Optional[np.ndarray]:
         return self.arrays.get("pulse_number")
 
+    def compute_pulse_numbers(self, model) -> None:
+        """Set the pulse numbers from `model` (toa.py:1984): the integer part of each TOA's
+        absolute phase (the device's phase minus the TZR TOA's) plus its delta_pulse_number,
+        i.e. the nearest integer number of turns; existing pulse numbers are replaced."""
+        hi, lo = model.phase(self, abs_phase=True)
+        ph = np.asarray(hi, dtype=np.longdouble) + np.asarray(lo, dtype=np.longdouble)
+        d = ph[:-1] - ph[-1] + np.asarray(self.arrays["delta_pulse_number"], dtype=np.longdouble)
+        self.arrays["pulse_number"] = np.round(d).astype(np.float64)
+
     def get_flag_value(self, flag: str, fill_value=None):
         col = self.flag_columns.get(flag)
         if col is None:
