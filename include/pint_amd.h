@@ -656,6 +656,8 @@ int pint_graph_launch(pint_ctx *ctx);
                                    tiles): every noise basis a PLRedNoise series of at most 63 modes */
 #define PINT_QUERY_NREUSE 5     /* pint_set_grid / pint_set_points calls of this context that kept the resident
                                    batch (same pulsar, point count and options) and only formed new tables */
+#define PINT_QUERY_NPLGLS 6     /* k_point_lnl_gls launches of this context (pint_point_lnlike_gls): a call refused
+                                   before any launch leaves it unchanged */
 int pint_query(pint_ctx *ctx, int key);
 /* The launch plan of the last pint_fit_step (host bookkeeping, no reference counterpart): which
  * kernel instantiations the call enqueued, as the dispatcher chose them from the batch's padded
@@ -802,6 +804,36 @@ int pint_set_dm_noise_classes(pint_ctx *ctx, int psr, int ncls, const int32_t *c
                               const double *dme0);
 int pint_point_lnlike(pint_ctx *ctx, int64_t ncls_tot, const double *cls_qf, int64_t ndmcls_tot,
                       const double *dmcls_qf, double *out);
+
+/* pint_point_lnlike_gls, after pint_eval(ctx, 0) like pint_point_lnlike: the marginalised
+ * correlated-noise log-likelihood of every instance k (Residuals.calc_chi2(lognorm=True),
+ * residuals.py:567-716, utils.py:3074 woodbury_dot), every instance with its own values:
+ *   cls_qf    (Q^2 [us^2], F) per TOA class, as for pint_point_lnlike: N_i = (sigma0_i^2 + Q^2) F^2 1e-12 s^2;
+ *   ep_phi    one prior variance (s^2) per ECORR epoch of the pulsar (pint_set_ecorr's order);
+ *   four_phi  the 2 nred prior variances (s^2) of the Fourier modes, PLRedNoise then PLDMNoise
+ *             (sin, cos per mode), the order of the pulsar's red_phi;
+ *   ones      1: the offset column of ones with Phi = 1e40 is appended (residuals.py:583-585, PHOFF
+ *             not free), 0: not (PHOFF free; the ECORR-only form of _calc_ecorr_chi2 is this case).
+ * With r the time residuals (the point's own weighted mean removed, none with a PhaseOffset),
+ * U = [Fourier columns | PLDMNoise columns times the row's (1400 MHz / f_bary)^2 | ECORR epoch
+ * indicators | ones], b = U^T N^-1 r and Sigma = Phi^-1 + U^T N^-1 U,
+ *   out[4k]     lnL = -chi2 / 2 - logdet C / 2,
+ *   out[4k + 1] chi2 = r^T N^-1 r - b^T Sigma^-1 b,
+ *   out[4k + 2] logdet C / 2 = (sum log N_i + sum log Phi_j + logdet Sigma) / 2,
+ *   out[4k + 3] logdet Sigma.
+ * The Fourier modes of each component must be the harmonics 1, 2, ... of the pulsar's first mode
+ * (get_rednoise_freqs' linspace(1/T, n/T, n)): the columns are rotations of the stored e^{i theta}.
+ * Where Sigma is not positive definite (cho_factor raises in the reference) the instance's four
+ * outputs are NaN and its PINT_E_SIGMA bit is raised (pint_inst_status); other instances are not
+ * affected.  Zero or NaN variances give what IEEE arithmetic gives the expressions above.
+ * ncls_tot / nep_tot / nphi_tot: the number of (Q^2, F) pairs, epoch variances and Fourier variances
+ * passed.  PINT_E_INVALID with a message, before any launch (PINT_QUERY_NPLGLS unchanged), when a
+ * pulsar of the batch has no noise classes, has wideband DM data (the wideband correlated likelihood
+ * is not implemented), has overlapping ECORR epochs or more than 128 columns 2 nred + ones, or a
+ * count is not the batch's sum.  Lazy mode: only enqueued (the arrays and out must stay valid until
+ * pint_check). */
+int pint_point_lnlike_gls(pint_ctx *ctx, int64_t ncls_tot, const double *cls_qf, int64_t nep_tot,
+                          const double *ep_phi, int64_t nphi_tot, const double *four_phi, int ones, double *out);
 
 #ifdef __cplusplus
 }

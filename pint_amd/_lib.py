@@ -209,6 +209,7 @@ def lib():
     L.pint_set_points.argtypes = [vp, C.c_int, C.c_int, dptr, C.c_int, C.POINTER(C.c_int32), dptr]
     L.pint_set_dm_noise_classes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dptr]
     L.pint_point_lnlike.argtypes = [vp, C.c_int64, dptr, C.c_int64, dptr, dptr]
+    L.pint_point_lnlike_gls.argtypes = [vp, C.c_int64, dptr, C.c_int64, dptr, C.c_int64, dptr, C.c_int, dptr]
     _lib = L
     L.pint_set_wideband.argtypes = [vp, C.c_int, dptr, dptr, dptr, C.POINTER(C.c_uint64)]
     L.pint_dm_resids.argtypes = [vp, C.c_int, C.c_int, dptr, dptr]
@@ -228,7 +229,7 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_apply_step_uniform", "pint_fit_step_apply", "pint_save_tables", "pint_restore_tables", "pint_read_norms",
             "pint_fit_step_enqueue", "pint_set_grid", "pint_add_pulsar_cols", "pint_pack_toas",
             "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms",
-            "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike"]
+            "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike", "pint_point_lnlike_gls"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

@@ -5876,6 +5876,241 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64) void k_point_lnl(
     }
 }
 
+// k_point_lnl_gls: the marginalised correlated-noise log-likelihood of every instance at its own
+// EFAC / EQUAD, ECORR and Fourier prior variances, after the residual pass
+// (Residuals.calc_chi2(lognorm=True), residuals.py:567-716, with utils.py:3074 woodbury_dot):
+//   lnL = -chi2 / 2 - logdet C / 2,  C = N + U Phi U^T,
+//   chi2 = r^T N^-1 r - b^T Sigma^-1 b,  b = U^T N^-1 r,  Sigma = Phi^-1 + U^T N^-1 U,
+//   logdet C = sum log N_i + sum log Phi_j + logdet Sigma.
+// One workgroup per instance.  r is k_point_lnl's (the point's own weighted mean, none with a
+// PhaseOffset), N_i = (sigma0_i^2 + Q_c^2) F_c^2 1e-12.  The columns of U kept dense are
+// G = [PLRedNoise sin, cos per harmonic | PLDMNoise the same times (1400 MHz / f_bary)^2 | ones],
+// generated per row by rotations of the stored e^{i theta}, e^{i 8 theta} (k_trig_setup; harmonic
+// k = a + 8 b is at most 7 rotations from the anchor e^{i 8 b theta}): no trigonometric function
+// per point.  The ECORR columns are disjoint epoch indicators and are eliminated first: epoch e
+// has the diagonal entry d_e = 1 / Phi_e + sum_{i in e} 1 / N_i and the row
+// g_e = sum_{i in e} [G_i | r_i] / N_i of Sigma, so its Schur complement is the rank-one term
+// -g_e g_e^T / d_e: a "virtual row" g_e of weight -1 / d_e after the n rows of weight 1 / N_i.
+// The rows are staged PG_R at a time in LDS ([G | r], one thread per row) and the augmented
+// Gram A = [G | r]^T W [G | r] is accumulated in 4x4 register tiles of its lower triangle (packed
+// in LDS, at most 33 x 33 / 2 tiles = 72 KB), every entry by one thread over the rows in order:
+// the same bits on every run.  Phi^-1 goes on the diagonal and a left-looking Cholesky over the
+// columns of G leaves L in place, y = L^-1 b in the row of r and chi2 = A_rr - y^T y.  A pivot
+// that is not > 0 (or NaN) gives four NaNs and raises the instance's PINT_E_SIGMA bit.
+// out[4k..4k+3] = lnL, chi2, logdet C / 2, logdet Sigma of the full Sigma (the eliminated epochs'
+// log d_e included).  off: per instance the first class, epoch and Fourier variance of its
+// values (null: instance k of one pulsar starts at k ncls, k nep, 2 k nred).
+constexpr int PG_MAXC = 128;  // columns of Sigma after the ECORR elimination
+constexpr int PG_R = 32;      // rows staged per chunk
+__device__ __forceinline__ int pg_at(int i, int j) {  // entry (i, j), j <= i, of the packed tiles
+    const int bi = i >> 2, bj = j >> 2;
+    return ((bi * (bi + 1) / 2 + bj) << 4) + ((i & 3) << 2) + (j & 3);
+}
+// x += sc [G_i | r]: the row's columns by rotations (sc = 1 on a zeroed x stores them exactly)
+__device__ __forceinline__ void pg_add_row(double* x, const PsrDev& Pd, int i, int nr, int nd, int ones, double D,
+                                           double sc, double r) {
+    const int nh = nr > nd ? nr : nd;
+    if (nh > 0) {
+        const double4_t z = ((gptr<double4_t>)Pd.red_cs)[i];
+        const double c1 = z[0], s1 = z[1], c8 = z[2], s8 = z[3];
+        double ca = 1.0, sa = 0.0, c = 1.0, s = 0.0;
+        const double sd = sc * D;
+        for (int k = 1; k <= nh; k++) {
+            if ((k & 7) == 0) {
+                rot(ca, sa, c8, s8);
+                c = ca;
+                s = sa;
+            } else {
+                rot(c, s, c1, s1);
+            }
+            if (k <= nr) {
+                x[2 * (k - 1)] += sc * s;
+                x[2 * (k - 1) + 1] += sc * c;
+            }
+            if (k <= nd) {
+                x[2 * (nr + k - 1)] += sd * s;
+                x[2 * (nr + k - 1) + 1] += sd * c;
+            }
+        }
+    }
+    const int m = 2 * (nr + nd) + ones;
+    if (ones) x[m - 1] += sc;
+    x[m] += sc * r;
+}
+__global__ __launch_bounds__(256) void k_point_lnl_gls(
+    const PsrDev* __restrict__ psrs, const InstDev* __restrict__ insts, const InstConst* __restrict__ ic,
+    const double* __restrict__ rphase, const double* __restrict__ ftay, const double* __restrict__ qf,
+    const double* __restrict__ epv, const double* __restrict__ fphi, const long* __restrict__ off, int ones,
+    double* __restrict__ out, int* __restrict__ istatus) {
+    extern __shared__ double lds[];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const InstDev I = insts[k];
+    const PsrDev& Pd = psrs[I.psr];
+    const pint_spec_t& S = *Pd.spec;
+    const int n = I.n, nep = Pd.nep;
+    const int nr = __builtin_amdgcn_readfirstlane(S.dmn0), nd = __builtin_amdgcn_readfirstlane(S.nred) - nr;
+    const int m = 2 * (nr + nd) + ones, W = m + 1, T = (W + 3) >> 2, nt = T * (T + 1) / 2, SP = 4 * T + 1;
+    double* A = lds;               // nt tiles of 16
+    double* X = A + 16 * nt;       // PG_R staged rows of SP
+    double* wg = X + PG_R * SP;    // their weights
+    double* sh = wg + PG_R;        // block_sums<4, 4>
+    const double* p = rphase + I.ooff;
+    const double* f = ftay + I.roff;
+    const double* Q = qf + 2 * (off ? off[3 * k] : (long)k * Pd.ncls);
+    const double* EP = epv + (off ? off[3 * k + 1] : (long)k * nep);
+    const double* PH = fphi + (off ? off[3 * k + 2] : (long)k * 2 * (nr + nd));
+    double mean = 0.0;
+    if (S.subtract_mean && S.weighted_mean) {  // (k_point_lnl's correction)
+        double v[2] = {0.0, 0.0};
+        for (int i = tid; i < n; i += 256) {
+            const int c = Pd.toa_cls[i];
+            const double s0 = Pd.sigma0[i], fc = Q[2 * c + 1];
+            const double w = 1.0 / ((s0 * s0 + Q[2 * c]) * (fc * fc));
+            v[0] += w * p[i];
+            v[1] += w;
+        }
+        block_sums<4, 2>(v, sh);
+        mean = v[0] / v[1];
+    }
+    for (int e = tid; e < 16 * nt; e += 256) A[e] = 0.0;
+    // the row's residual, variance and DM-noise scale
+    const InstConst& C = ic[k];
+    auto row = [&](int i, double& r, double& N, double& D) {
+        const int c = Pd.toa_cls[i];
+        const double s0 = Pd.sigma0[i], fc = Q[2 * c + 1];
+        N = (s0 * s0 + Q[2 * c]) * (fc * fc) * 1e-12;
+        r = (p[i] - mean) / f[i];
+        D = 1.0;
+        if (nd > 0) {
+            const double bf = bary_freq_row(Pd, S, C, dd_make(Pd.tdb_hi[i], Pd.tdb_lo[i]), i);
+            D = 1400.0 * 1400.0 * (1.0 / (bf * bf));
+        }
+    };
+    // the thread's tiles (at most three of the 561)
+    int tbi[3], tbj[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const int t = tid + 256 * q;
+        int bi = 0;
+        while ((bi + 1) * (bi + 2) / 2 <= t) bi++;
+        tbi[q] = bi;
+        tbj[q] = t - bi * (bi + 1) / 2;
+    }
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};  // sum log N, sum log Phi, sum log d_e, epochs whose d_e is not > 0
+    const int nrows = n + nep;
+    for (int c0 = 0; c0 < nrows; c0 += PG_R) {
+        const int nc = nrows - c0 < PG_R ? nrows - c0 : PG_R;
+        __syncthreads();
+        for (int e = tid; e < nc * SP; e += 256) X[e] = 0.0;
+        __syncthreads();
+        if (tid < nc) {
+            double* x = X + tid * SP;
+            const int rw = c0 + tid;
+            double r, N, D;
+            if (rw < n) {
+                row(rw, r, N, D);
+                pg_add_row(x, Pd, rw, nr, nd, ones, D, 1.0, r);
+                wg[tid] = 1.0 / N;
+                sums[0] += log(N);
+            } else {
+                const int e = rw - n;
+                double v = 0.0;
+                for (int q = Pd.ep_ptr[e]; q < Pd.ep_ptr[e + 1]; q++) {
+                    const int i = Pd.ep_idx[q];
+                    row(i, r, N, D);
+                    const double iN = 1.0 / N;
+                    pg_add_row(x, Pd, i, nr, nd, ones, D, iN, r);
+                    v += iN;
+                }
+                const double phi = EP[e], d = 1.0 / phi + v;
+                wg[tid] = -1.0 / d;
+                sums[1] += log(phi);
+                sums[2] += log(d);
+                if (!(d > 0.0)) sums[3] += 1.0;  // (Sigma's diagonal entry: not positive definite)
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            if (tid + 256 * q < nt) {
+                const int bi = tbi[q], bj = tbj[q];
+                double* At = A + 16 * (tid + 256 * q);
+                double acc[16];
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc[e] = At[e];
+                for (int rr = 0; rr < nc; rr++) {
+                    const double* x = X + rr * SP;
+                    const double w = wg[rr];
+                    double a[4], b[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        a[u] = x[4 * bi + u] * w;
+                        b[u] = x[4 * bj + u];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+#pragma unroll
+                        for (int v = 0; v < 4; v++) acc[4 * u + v] += a[u] * b[v];
+                }
+#pragma unroll
+                for (int e = 0; e < 16; e++) At[e] = acc[e];
+            }
+        }
+    }
+    __syncthreads();
+    // Sigma's diagonal: 1 / Phi_j (the ones column: Phi = 1e40, residuals.py:583-585)
+    if (tid < m) {
+        const double phi = (ones && tid == m - 1) ? 1e40 : PH[tid];
+        A[pg_at(tid, tid)] += 1.0 / phi;
+        sums[1] += log(phi);
+    }
+    __syncthreads();
+    // left-looking Cholesky over the columns of G, the row of r carried along; every thread forms
+    // the pivot itself (one barrier per column)
+    double ldet = 0.0;
+    bool bad = false;
+    for (int j = 0; j < m; j++) {
+        double vi = 0.0, vj = A[pg_at(j, j)];
+        const bool mine = tid >= j && tid < W;
+        if (mine) vi = A[pg_at(tid, j)];
+        for (int q = 0; q < j; q++) {
+            const double ljq = A[pg_at(j, q)];
+            vj -= ljq * ljq;
+            if (mine) vi -= A[pg_at(tid, q)] * ljq;
+        }
+        if (!(vj > 0.0)) {  // (uniform: not positive definite, or NaN)
+            bad = true;
+            break;
+        }
+        const double sd = sqrt(vj);
+        ldet += log(vj);
+        __syncthreads();
+        if (mine) A[pg_at(tid, j)] = tid == j ? sd : vi / sd;
+        __syncthreads();
+    }
+    block_sums<4, 4>(sums, sh);
+    if (tid == 0) {
+        double* o = out + 4 * (long)k;
+        if (bad || sums[3] != 0.0) {
+            const double nan = __builtin_nan("");
+            o[0] = o[1] = o[2] = o[3] = nan;
+            atomicOr(&istatus[k], 1 << PINT_E_SIGMA);
+        } else {
+            double chi2 = A[pg_at(m, m)];
+            for (int q = 0; q < m; q++) {
+                const double y = A[pg_at(m, q)];
+                chi2 -= y * y;
+            }
+            const double lds_ = ldet + sums[2];
+            const double ln = 0.5 * (sums[0] + sums[1] + lds_);
+            o[0] = -(0.5 * chi2 + ln);
+            o[1] = chi2;
+            o[2] = ln;
+            o[3] = lds_;
+        }
+    }
+}
+
 // Debug/parity introspection (pint_debug_gram): the assembled, unnormalised normal matrix
 // [M | r]^T N^-1 [M | r] of the last pint_fit_step in the original column order (the ECORR
 // block already eliminated by its Schur complement), (K+1)^2 per instance, followed by the K
@@ -6253,6 +6488,9 @@ struct pint_ctx {
     size_t nz_cap = 0;
     double* d_pl = nullptr;  // pint_point_lnlike scratch (class parameters, offsets, outputs)
     size_t pl_cap = 0;
+    double* d_pg = nullptr;  // pint_point_lnlike_gls scratch (class, epoch and Fourier values, offsets, outputs)
+    size_t pg_cap = 0;
+    int n_plgls = 0;         // k_point_lnl_gls launches of this context (PINT_QUERY_NPLGLS)
     int n_batch_reuse = 0;   // pint_set_grid / pint_set_points calls that kept the resident batch (PINT_QUERY_NREUSE)
     double* d_noise = nullptr;  // pint_noise_resids: red and ECORR realisations (2 tot_out)
     long noise_cap = 0;
@@ -6894,6 +7132,7 @@ void pint_ctx_destroy(pint_ctx* ctx) {
     if (ctx->d_dmc2) hipFree(ctx->d_dmc2);
     if (ctx->d_nz) hipFree(ctx->d_nz);
     if (ctx->d_pl) hipFree(ctx->d_pl);
+    if (ctx->d_pg) hipFree(ctx->d_pg);
     if (ctx->d_status_slots) hipFree(ctx->d_status_slots);
     if (ctx->h_status) hipHostFree(ctx->h_status);
     for (int sl = 0; sl < pint_ctx::NSLOT; sl++) {
@@ -9472,6 +9711,7 @@ int pint_query(pint_ctx* ctx, int key) {
     if (key == PINT_QUERY_NSPINEVAL) return ctx->n_spin_eval;
     if (key == PINT_QUERY_WFUSE) return ctx->wfuse ? 1 : 0;
     if (key == PINT_QUERY_NREUSE) return ctx->n_batch_reuse;
+    if (key == PINT_QUERY_NPLGLS) return ctx->n_plgls;
     ctx->err = "unknown query";
     return -PINT_E_INVALID;
 }
@@ -10109,6 +10349,86 @@ int pint_point_lnlike(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf, int
 #undef PINT_PL_ARGS
     HIPCHK(hipGetLastError());
     HIPCHK(d2h(out, d_out, sizeof(double) * 5 * ni, ctx->stream));
+    if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+int pint_point_lnlike_gls(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf, int64_t nep_tot, const double* ep_phi,
+                          int64_t nphi_tot, const double* four_phi, int ones, double* out) {
+    if (!ctx || ctx->ninst <= 0 || !cls_qf || !out || ones < 0 || ones > 1) return PINT_E_INVALID;
+    const int ni = ctx->ninst;
+    // every check before any launch
+    long nq = 0, ne = 0, nf = 0;
+    int maxw = 0;
+    const bool one = ctx->upsr.size() == 1;
+    std::vector<long> off;
+    if (!one) off.resize(3 * (size_t)ni);
+    for (int k = 0; k < (one ? 1 : ni); k++) {
+        const PsrHost& ph = ctx->psrs[ctx->inst[k].psr];
+        const PsrDev& d = ph.dev;
+        if (d.ncls <= 0) { ctx->err = "pint_point_lnlike_gls: no noise classes (pint_set_noise_classes)"; return PINT_E_INVALID; }
+        if (d.wb) { ctx->err = "pint_point_lnlike_gls: wideband DM data (the wideband correlated likelihood is not implemented)"; return PINT_E_INVALID; }
+        if (d.nep > 0 && d.ep_overlap) { ctx->err = "pint_point_lnlike_gls: overlapping ECORR epochs"; return PINT_E_INVALID; }
+        const int ncolumns = 2 * ph.spec.nred + ones;
+        if (ncolumns > PG_MAXC) {
+            ctx->err = "pint_point_lnlike_gls: " + std::to_string(ncolumns) + " columns of Sigma (2 (TNREDC + TNDMC) + the offset " +
+                       "column), at most " + std::to_string(PG_MAXC);
+            return PINT_E_INVALID;
+        }
+        maxw = std::max(maxw, ncolumns + 1);
+        if (one) {
+            nq = (long)ni * d.ncls;
+            ne = (long)ni * d.nep;
+            nf = (long)ni * 2 * ph.spec.nred;
+        } else {
+            off[3 * k] = nq;
+            off[3 * k + 1] = ne;
+            off[3 * k + 2] = nf;
+            nq += d.ncls;
+            ne += d.nep;
+            nf += 2 * ph.spec.nred;
+        }
+    }
+    if ((ne > 0 && !ep_phi) || (nf > 0 && !four_phi)) {
+        ctx->err = "pint_point_lnlike_gls: ECORR epochs or Fourier modes without their variances";
+        return PINT_E_INVALID;
+    }
+    if (ncls_tot != nq || nep_tot != ne || nphi_tot != nf) {
+        ctx->err = "pint_point_lnlike_gls: counts do not match the batch (" + std::to_string(ncls_tot) + " / " +
+                   std::to_string(nq) + " TOA classes, " + std::to_string(nep_tot) + " / " + std::to_string(ne) +
+                   " ECORR epochs, " + std::to_string(nphi_tot) + " / " + std::to_string(nf) + " Fourier variances)";
+        return PINT_E_INVALID;
+    }
+    flush_r2(ctx);
+    hipSetDevice(ctx->device);
+    if (flush_setup(ctx)) return PINT_E_HIP;  // (the rows' e^{i theta}: red_cs)
+    // scratch: qf 2 nq | epv ne | fphi nf | out 4 ni | off 3 ni (as doubles' storage)
+    const size_t need = (size_t)2 * nq + ne + nf + 4 * ni + 3 * ni;
+    if (need > ctx->pg_cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a lazy call's kernel may still read the old one)
+        if (ctx->d_pg) hipFree(ctx->d_pg);
+        ctx->d_pg = nullptr;
+        ctx->pg_cap = 0;
+        HIPCHK(hipMalloc(&ctx->d_pg, sizeof(double) * need));
+        ctx->pg_cap = need;
+    }
+    double* d_q = ctx->d_pg;
+    double* d_e = d_q + 2 * nq;
+    double* d_f = d_e + ne;
+    double* d_out = d_f + nf;
+    long* d_off = (long*)(d_out + 4 * ni);
+    static_assert(sizeof(long) == sizeof(double), "offset packing");
+    HIPCHK(h2d(d_q, cls_qf, sizeof(double) * 2 * nq, ctx->stream, false));
+    if (ne > 0) HIPCHK(h2d(d_e, ep_phi, sizeof(double) * ne, ctx->stream, false));
+    if (nf > 0) HIPCHK(h2d(d_f, four_phi, sizeof(double) * nf, ctx->stream, false));
+    if (!one) HIPCHK(h2d(d_off, off.data(), sizeof(long) * off.size(), ctx->stream, true));
+    const int T = (maxw + 3) / 4;
+    const size_t lds = sizeof(double) * ((size_t)16 * (T * (T + 1) / 2) + (size_t)PG_R * (4 * T + 1) + PG_R + 16);
+    hipLaunchKernelGGL(k_point_lnl_gls, dim3(ni), dim3(256), lds, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_ic,
+                       ctx->d_rp, ctx->d_ftay, d_q, d_e, d_f, one ? nullptr : d_off, ones, d_out, ctx->d_istatus);
+    HIPCHK(hipGetLastError());
+    ctx->n_plgls++;
+    HIPCHK(d2h(out, d_out, sizeof(double) * 4 * ni, ctx->stream));
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }

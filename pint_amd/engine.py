@@ -1461,6 +1461,37 @@ class Session:
             self._keep += [q, dq]
         return out.reshape(ni, 5)
 
+    def n_point_lnlike_gls(self):
+        """k_point_lnl_gls launches of this context (PINT_QUERY_NPLGLS)."""
+        return int(self.L.pint_query(self.ctx, 6))
+
+    def point_lnlike_gls(self, cls_qf, ep_phi, four_phi, ones):
+        """k_point_lnl_gls over the batch, after eval(False): out [ninst, 4] = (lnL, chi2, logdet C / 2,
+        logdet Sigma) of the marginalised correlated-noise likelihood -- see include/pint_amd.h
+        pint_point_lnlike_gls.  cls_qf: (Q^2, F) per TOA class and instance; ep_phi: a variance (s^2)
+        per ECORR epoch and instance (None: no epochs); four_phi: the 2 nred Fourier prior variances
+        per instance (None: no Fourier modes); ones: the 1e40 offset column.  Lazy: a pinned buffer,
+        complete after check()."""
+        for lay in {id(l): l for l in self.inst_layout}.values():
+            f = lay.red_freq
+            for a, b in ((0, lay.spec.dmn0), (lay.spec.dmn0, lay.nred)) if f is not None else ():
+                if b > a:
+                    k = np.arange(1, b - a + 1)
+                    fl = np.asarray(f, dtype=np.longdouble)
+                    if np.any(np.abs(fl[a:b] - k * fl[0]) > 1e-15 * np.abs(fl[a:b])):
+                        raise ValueError("point_lnlike_gls: the Fourier modes of a noise component are not the "
+                                         "harmonics 1..n of the pulsar's first mode")
+        q = np.ascontiguousarray(cls_qf, dtype=np.float64).reshape(-1)
+        e = None if ep_phi is None else np.ascontiguousarray(ep_phi, dtype=np.float64).reshape(-1)
+        p = None if four_phi is None else np.ascontiguousarray(four_phi, dtype=np.float64).reshape(-1)
+        ni = len(self.inst_layout)
+        out = self._pin("ptlnlg", 4 * ni) if self.lazy else np.empty(4 * ni)
+        self._check(self.L.pint_point_lnlike_gls(self.ctx, q.size // 2, L.ptr(q), 0 if e is None else e.size, L.ptr(e),
+                                                 0 if p is None else p.size, L.ptr(p), 1 if ones else 0, L.ptr(out)))
+        if self.lazy:
+            self._keep += [q, e, p]
+        return out.reshape(ni, 4)
+
     def debug_set_resids(self, resids):
         """Replace every instance's time residuals (list of n-arrays, seconds)."""
         flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64) for r in resids]))
