@@ -835,6 +835,51 @@ int pint_point_lnlike(pint_ctx *ctx, int64_t ncls_tot, const double *cls_qf, int
 int pint_point_lnlike_gls(pint_ctx *ctx, int64_t ncls_tot, const double *cls_qf, int64_t nep_tot,
                           const double *ep_phi, int64_t nphi_tot, const double *four_phi, int ones, double *out);
 
+/* ---- photon events (scripts/event_optimize.py, eventstats.py) --------------------------------
+ * The rows of a pulsar taken as photons: after pint_eval(ctx, 0) the absolute phase of every row of
+ * every instance is on the device, and the two calls below consume it as photon phases
+ *   phi_i = frac(phase_i)  (abs_phase 0)   or   frac(phase_i - phase_TZR)  (abs_phase 1)
+ * -- the reference's model.phase(toas, abs_phase=...).frac % 1 --, the fraction d - floor(d) taken in
+ * double-double, rounded to a double and kept in [0, 1).
+ *
+ * pint_set_photons: the pulsar's photon data, beside its spec (calling rule of pint_set_wavex, at any
+ * time after pint_add_pulsar; a second call replaces the data).  weights: n doubles (the pulsar's
+ * row count), or NULL for unweighted data.  tmpl: nbin doubles, 1 <= nbin <= PINT_MAX_TEMPLATE, the
+ * template at the phases j / nbin; or NULL with nbin 0 for no template (only the trig sums are then
+ * available).  The library keeps device copies and frees them with the context.  PINT_E_INVALID with a
+ * message for a bad pulsar, abs_phase, count or pointer; the pulsar's previous data stay in force.
+ *
+ * pint_point_photon_lnlike: for every instance k and each of its nphs (1..PINT_MAX_PHOTON_PHS) phase
+ * offsets phs[k nphs + j],
+ *   out[k nphs + j] = sum_i log(w_i T(x_ij) + 1 - w_i)   (sum_i log T(x_ij) without weights),
+ *   x_ij = (phi_i + phs[k nphs + j]) mod 1 formed in doubles (event_optimize.py:143-145),
+ *   T(x) = np.interp(x, arange(L) / L, tmpl, right=tmpl[0]): linear between the nodes j / L and
+ *          (j + 1) / L for j < L - 1, and the constant tmpl[0] for x > (L - 1) / L -- a step at the last
+ *          node, not an interpolation back to bin 0.
+ * One offset per instance is emcee_fitter.lnposterior's likelihood; many offsets at one point are
+ * marginalize_over_phase's scan at the cost of one evaluation.  A non-positive argument of the log
+ * gives what IEEE arithmetic gives the reference (-inf, NaN) for that output only.
+ *
+ * pint_point_photon_trig: for every instance k and m (1..PINT_MAX_PHOTON_HARM) harmonics, 2 m + 2
+ * doubles:
+ *   out[k (2m + 2) + 2 (j - 1)]     = sum_i w_i cos(2 pi j phi_i),
+ *   out[k (2m + 2) + 2 (j - 1) + 1] = sum_i w_i sin(2 pi j phi_i),   j = 1..m,
+ *   then sum_i w_i and sum_i w_i^2  (w = 1 without weights):
+ * the sums z2m, z2mw, hm, hmw and em_four are made of.
+ *
+ * Both: every output has the same bits on every run and whatever the batch around the instance
+ * (fixed-order sums, no floating-point atomics); batches of several pulsars work, each with its own
+ * data.  PINT_E_INVALID with a message, before any launch, when a pulsar of the batch has no photon
+ * data (or no template, for the likelihood), a count is out of range, or the batch was not evaluated (no pint_eval since pint_set_instances /
+ * pint_set_grid / pint_set_points / pint_set_tables, an applied step or pint_restore_tables).  Lazy
+ * mode: only enqueued (phs and out must stay valid until pint_check), like pint_point_lnlike. */
+#define PINT_MAX_TEMPLATE 4096     /* template bins: the table sits in LDS beside the reduction scratch */
+#define PINT_MAX_PHOTON_PHS 1024   /* phase offsets per instance and call */
+#define PINT_MAX_PHOTON_HARM 64    /* harmonics of the trig sums */
+int pint_set_photons(pint_ctx *ctx, int psr, int abs_phase, const double *weights, int nbin, const double *tmpl);
+int pint_point_photon_lnlike(pint_ctx *ctx, int nphs, const double *phs, double *out);
+int pint_point_photon_trig(pint_ctx *ctx, int m, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,4 +24,14 @@ def __getattr__(name):
     if name == "BayesianTiming":
         from .bayesian import BayesianTiming
         return BayesianTiming
+    # the photon-event modules (event_optimize needs scipy.stats too): the same rule
+    if name == "PhotonTiming":
+        from .event_optimize import PhotonTiming
+        return PhotonTiming
+    if name == "get_event_TOAs":
+        from .event_toas import get_event_TOAs
+        return get_event_TOAs
+    if name in ("eventstats", "event_optimize", "event_toas"):
+        import importlib
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

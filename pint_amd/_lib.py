@@ -32,6 +32,9 @@ MAX_PW = 64       # PINT_MAX_PW: PiecewiseSpindown pieces (col_index = 4 * piece
 PW_NPAR = 7       # PINT_PW_NPAR: PWEP, PWSTART, PWSTOP, PWPH, PWF0, PWF1, PWF2 (one dd pair each)
 MAX_WAVE = 128    # PINT_MAX_WAVE: Wave terms
 MAX_IFUNC = 1024  # PINT_MAX_IFUNC: IFunc control points
+MAX_TEMPLATE = 4096     # PINT_MAX_TEMPLATE: photon template bins
+MAX_PHOTON_PHS = 1024   # PINT_MAX_PHOTON_PHS: phase offsets per instance and call
+MAX_PHOTON_HARM = 64    # PINT_MAX_PHOTON_HARM: harmonics of the photon trig sums
 
 PINT_OK, PINT_E_INVALID, PINT_E_HIP, PINT_E_NOT_PD, PINT_E_KEPLER, PINT_E_PARAM, PINT_E_SIGMA = range(7)
 
@@ -210,6 +213,9 @@ def lib():
     L.pint_set_dm_noise_classes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dptr]
     L.pint_point_lnlike.argtypes = [vp, C.c_int64, dptr, C.c_int64, dptr, dptr]
     L.pint_point_lnlike_gls.argtypes = [vp, C.c_int64, dptr, C.c_int64, dptr, C.c_int64, dptr, C.c_int, dptr]
+    L.pint_set_photons.argtypes = [vp, C.c_int, C.c_int, dptr, C.c_int, dptr]
+    L.pint_point_photon_lnlike.argtypes = [vp, C.c_int, dptr, dptr]
+    L.pint_point_photon_trig.argtypes = [vp, C.c_int, dptr]
     _lib = L
     L.pint_set_wideband.argtypes = [vp, C.c_int, dptr, dptr, dptr, C.POINTER(C.c_uint64)]
     L.pint_dm_resids.argtypes = [vp, C.c_int, C.c_int, dptr, dptr]
@@ -229,7 +235,8 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_apply_step_uniform", "pint_fit_step_apply", "pint_save_tables", "pint_restore_tables", "pint_read_norms",
             "pint_fit_step_enqueue", "pint_set_grid", "pint_add_pulsar_cols", "pint_pack_toas",
             "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms",
-            "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike", "pint_point_lnlike_gls"]
+            "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike", "pint_point_lnlike_gls",
+            "pint_set_photons", "pint_point_photon_lnlike", "pint_point_photon_trig"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

@@ -40,8 +40,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib as L
-from .priors import Prior, UniformUnboundedRV
+from .pointbatch import PointBatch
 
 LD = np.longdouble
 WHITE = ("EFAC", "EQUAD", "DMEFAC", "DMEQUAD")
@@ -49,7 +48,6 @@ RED = ("TNREDAMP", "TNREDGAM", "RNAMP", "RNIDX")
 DMN = ("TNDMAMP", "TNDMGAM")
 FYR = 1 / 3.16e7  # (noise_model.py powerlaw)
 RN_FAC = (86400.0 * 365.24 * 1e6) / (2.0 * np.pi * np.sqrt(3.0))  # RNAMP -> amplitude (noise_model.py:761-768)
-EVAL_ERRORS = (L.PINT_E_KEPLER, L.PINT_E_PARAM)
 
 
 def _base(name: str) -> str:
@@ -76,12 +74,7 @@ def _rowpow(ff: np.ndarray, e: np.ndarray) -> np.ndarray:
     return out
 
 
-def _is_unbounded(prior) -> bool:
-    rv = prior._rv
-    return isinstance(rv, UniformUnboundedRV) or isinstance(getattr(rv, "dist", None), UniformUnboundedRV)
-
-
-class BayesianTiming:
+class BayesianTiming(PointBatch):
     """lnprior, prior_transform, lnlikelihood and lnposterior of a timing model and TOAs.
 
     model : the timing model; a deep copy is kept, its values are the base values of every batch.
@@ -97,7 +90,6 @@ class BayesianTiming:
     """
 
     def __init__(self, model, toas, use_pulse_numbers=False, prior_info=None, correlated_noise=False):
-        from scipy.stats import norm, uniform
         self.model = copy.deepcopy(model)
         self.toas = toas
         if use_pulse_numbers:
@@ -109,15 +101,7 @@ class BayesianTiming:
         self.param_labels = self.model.free_params
         self.params = [self.model[p] for p in self.param_labels]
         self.nparams = len(self.param_labels)
-        if prior_info is not None:
-            for par, info in prior_info.items():
-                distr = info["distr"]
-                if distr == "uniform":
-                    self.model[par].prior = Prior(uniform(info["pmin"], info["pmax"] - info["pmin"]))
-                elif distr == "normal":
-                    self.model[par].prior = Prior(norm(info["mu"], info["sigma"]))
-                else:
-                    raise NotImplementedError("Only uniform and normal distributions are supported in prior_info.")
+        self._apply_prior_info(prior_info)
         self.correlated_noise = bool(correlated_noise)
         self._validate_priors()
         self.likelihood_method = self._decide_likelihood_method()
@@ -125,11 +109,6 @@ class BayesianTiming:
         self._dev = None
 
     # -- construction ------------------------------------------------------------------
-    def _validate_priors(self):
-        for p in self.params:
-            if _is_unbounded(p.prior):
-                raise NotImplementedError(f"Unbounded uniform priors are not supported. (param : {p.name})")
-
     def _decide_likelihood_method(self):
         m = self.model
         if not m.has_correlated_errors:
@@ -253,45 +232,7 @@ class BayesianTiming:
             self._dev = s
         return self._dev
 
-    def close(self):
-        if getattr(self, "_dev", None) is not None:
-            self._dev.close()
-            self._dev = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # -- arguments ---------------------------------------------------------------------
-    def _points(self, params, batch):
-        v = np.asarray(params)
-        if v.dtype != LD:
-            v = v.astype(np.float64)
-        if not batch:
-            if v.ndim != 1 or len(v) != self.nparams:
-                raise IndexError(f"The number of input parameters ({len(params)}) should be the same "
-                                 f"as the number of free parameters ({self.nparams}).")
-            return v[None, :]
-        if v.ndim != 2 or v.shape[1] != self.nparams:
-            raise IndexError(f"The number of input parameters ({v.shape[-1] if v.ndim else 0}) should be the same "
-                             f"as the number of free parameters ({self.nparams}).")
-        return v
-
-    # -- prior -------------------------------------------------------------------------
-    def lnprior_batch(self, params):
-        """The factorised log-prior of every point, (N,); -inf where any parameter's is -inf or NaN."""
-        v = self._points(params, True)
-        total = np.zeros(v.shape[0])
-        with np.errstate(invalid="ignore", divide="ignore"):
-            for j, p in enumerate(self.params):
-                total = total + np.asarray(p.prior_pdf(np.ascontiguousarray(v[:, j]), logpdf=True), dtype=np.float64)
-        return np.where(np.isnan(total), -np.inf, total)
-
-    def lnprior(self, params):
-        return float(self.lnprior_batch(self._points(params, False))[0])
-
+    # -- prior (lnprior, lnprior_batch and the argument check: PointBatch) ----------------
     def prior_transform_batch(self, cube):
         """Points of the unit hypercube mapped to the prior distribution, (N, nparams) float64."""
         c = np.asarray(cube, dtype=np.float64)
@@ -321,13 +262,10 @@ class BayesianTiming:
             out[:, c, 0], out[:, c, 1] = q2, f
         return out
 
-    def _chunk(self, n):
-        from .gridutils import GRID_BATCH_BYTES
-        lay = self.lay
-        per_pt = 8.0 * (lay.n * (lay.K + 12) + 64 * (lay.K + 2) ** 2)
+    def _extra_point_bytes(self):
         if self.likelihood_method == "gls":  # (class, epoch and Fourier values, outputs)
-            per_pt += 8.0 * (2 * len(self._cls[2]) + len(self._ep) + len(self._ff) + 4)
-        return int(max(1, min(n, GRID_BATCH_BYTES // per_pt)))
+            return 8.0 * (2 * len(self._cls[2]) + len(self._ep) + len(self._ff) + 4)
+        return 0.0
 
     def lnlikelihood_terms_batch(self, params):
         """(N, 5) of every point; a point the device flags (pint_inst_status) is NaN.
@@ -335,21 +273,11 @@ class BayesianTiming:
         the reference takes it).  "gls": lnL, chi2 = r^T C^-1 r, log det C / 2, log det Sigma, 0."""
         v = self._points(params, True)
         s = self._device()
-        lay = self.lay
         out = np.empty((v.shape[0], 5))
-        names = [p for _, p in self._timing]
-        cols = [j for j, _ in self._timing]
         chunk = self._chunk(v.shape[0])
         for c0 in range(0, v.shape[0], chunk):
             vc = v[c0:c0 + chunk]
-            s.set_points(lay, self._table0, names, vc[:, cols])
-            flagged = False
-            try:
-                s.eval(False)
-            except L.PintError as e:
-                if e.code not in EVAL_ERRORS:
-                    raise
-                flagged = True
+            flagged = self._eval_points(s, vc)
             if self.likelihood_method == "gls":
                 if flagged:
                     bad = s.inst_status() != 0

@@ -6111,6 +6111,175 @@ __global__ __launch_bounds__(256) void k_point_lnl_gls(
     }
 }
 
+// ---------------------------------------------------------------------------------
+// photon events (pint_set_photons): the evaluation's absolute phases consumed as photon phases
+// ---------------------------------------------------------------------------------
+// A pulsar's photon data, beside its PsrDev (indexed alike; the evaluation kernels never see it).
+struct PhotDev {
+    const double* w;     // n weights (null: unweighted)
+    const double* tmpl;  // nbin template values (null: no template)
+    int nbin;
+    int has;             // pint_set_photons was called for the pulsar
+    int abs_phase;       // 1: the row's phase minus the TZR row's, 0: the row's phase
+    double edge;         // (nbin - 1) / nbin as the reference's arange(L) / L forms it: the last node
+};
+
+// the photon phase of row i: the fractional part of the row's absolute phase (minus the TZR row's),
+// taken in double-double, rounded to a double and kept in [0, 1)
+__device__ __forceinline__ double photon_phase(const double* __restrict__ ph_hi, const double* __restrict__ ph_lo, long r,
+                                               bool abs_phase, dd tz) {
+    dd d = dd_make(ph_hi[r], ph_lo[r]);
+    if (abs_phase) d = dd_sub(d, tz);
+    double f = dd_to_d(dd_sub(d, dd_floor(d)));
+    if (f >= 1.0) f = 0x1.fffffffffffffp-1;  // (a fraction within half an ulp of 1)
+    return f < 0.0 ? 0.0 : f;
+}
+
+// k_photon_lnl: the template likelihood of every instance at each of its nphs phase offsets, after
+// the evaluation (event_optimize.py:137-149 profile_likelihood at every offset):
+//   out[k nphs + j] = sum_i log(w_i T(x_ij) + 1 - w_i)  (sum_i log T(x_ij) without weights),
+//   x_ij = (phi_i + phs[k nphs + j]) mod 1 in doubles, T = np.interp(x, arange(L) / L, tmpl, right=tmpl[0]):
+// linear between the nodes j / L, the constant tmpl[0] beyond the last node (L - 1) / L.
+// One workgroup per (instance, tile of PH_J offsets); the template (L + 1 doubles, its last entry
+// repeated) is staged in LDS once, each photon's phase is formed once per tile and serves the tile's
+// offsets.  Every sum is a thread's strided partial, then block_sums' fixed order, so a point's bits
+// depend on its own n and nphs only.  Reads 16 B (24 B with weights) per photon and tile.
+constexpr int PH_J = 8;   // offsets per workgroup
+constexpr int PH_BT = 256;
+static_assert(PINT_MAX_TEMPLATE * sizeof(double) + 4096 <= 65536, "the template and the reduction scratch share the LDS");
+
+__device__ __forceinline__ double photon_template(const double* __restrict__ tab, int L, double edge, double x) {
+    if (x > edge) return tab[0];  // (np.interp's right=tmpl[0]: a step at the last node)
+    const double xl = x * (double)L;
+    const int j = max(0, min((int)xl, L - 2));
+    const double t = fma(x, (double)L, -(double)j);
+    return fma(t, tab[j + 1] - tab[j], tab[j]);
+}
+// one photon's term at one offset, the sums in the reference's order (weights * probs + 1.0 - weights)
+__device__ __forceinline__ double photon_term(const double* __restrict__ tab, int L, double edge, double phi, double off,
+                                              double w, bool weighted) {
+    DD_NOCONTRACT
+    const double s = phi + off;
+    const double x = s - floor(s);  // (numpy's mod 1 of a double: exact for s >= 0)
+    const double p = photon_template(tab, L, edge, x);
+    return log(weighted ? (w * p + 1.0) - w : p);
+}
+
+__global__ __launch_bounds__(PH_BT) void k_photon_lnl(const InstDev* __restrict__ insts, const PhotDev* __restrict__ phot,
+                                                       const double* __restrict__ ph_hi, const double* __restrict__ ph_lo,
+                                                       int nphs, const double* __restrict__ phs, double* __restrict__ out) {
+    __shared__ double tab[PINT_MAX_TEMPLATE + 1];
+    __shared__ double sh[PH_J * (PH_BT / 64)];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const int n = insts[k].n;
+    const long ro = insts[k].roff;
+    const PhotDev P = phot[insts[k].psr];
+    const int L = P.nbin;
+    const int j0 = blockIdx.y * PH_J, jn = min(PH_J, nphs - j0);
+    for (int e = tid; e <= L; e += PH_BT) tab[e] = P.tmpl[min(e, L - 1)];
+    double off[PH_J], acc[PH_J];
+#pragma unroll
+    for (int j = 0; j < PH_J; j++) {
+        off[j] = phs[(long)k * nphs + j0 + min(j, jn - 1)];
+        acc[j] = 0.0;
+    }
+    const dd tz = dd_make(ph_hi[ro + n], ph_lo[ro + n]);
+    __syncthreads();
+    for (int i = tid; i < n; i += PH_BT) {
+        const double phi = photon_phase(ph_hi, ph_lo, ro + i, P.abs_phase != 0, tz);
+        const double w = P.w ? P.w[i] : 1.0;
+#pragma unroll
+        for (int j = 0; j < PH_J; j++) {
+            if (j >= jn) break;  // (uniform over the workgroup)
+            acc[j] += photon_term(tab, L, P.edge, phi, off[j], w, P.w != nullptr);
+        }
+    }
+    block_sums<PH_BT / 64, PH_J>(acc, sh);
+    if (tid == 0) {
+#pragma unroll
+        for (int j = 0; j < PH_J; j++)
+            if (j < jn) out[(long)k * nphs + j0 + j] = acc[j];
+    }
+}
+
+// k_photon_trig: the weighted trigonometric sums of every instance's photon phases,
+//   out[k (2 m + 2) + ...] = C_1, S_1, ..., C_m, S_m, sum w, sum w^2,
+//   C_j = sum_i w_i cos(2 pi j phi_i), S_j = sum_i w_i sin(2 pi j phi_i)  (w = 1 without weights):
+// what z2m, z2mw, hm, hmw and em_four are made of (eventstats.py).  One workgroup per instance, one
+// sincospi per photon; the harmonics follow by rotations e^{i j t} = e^{i (j - 1) t} e^{i t} re-anchored
+// every 8 by the squarings e^{i 8 t} (so harmonic j is at most 3 squarings, j / 8 anchor products and 8
+// rotations from the sincos), accumulated in MC (the cap on m of the instantiation) register pairs
+// per thread.  Strided partials, then block_sums' fixed order.  Reads 16 B (24 B) per photon.
+template <int MC>
+__global__ __launch_bounds__(PH_BT) void k_photon_trig(const InstDev* __restrict__ insts, const PhotDev* __restrict__ phot,
+                                                        const double* __restrict__ ph_hi, const double* __restrict__ ph_lo,
+                                                        int m, double* __restrict__ out) {
+    __shared__ double sh[8 * (PH_BT / 64)];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const int n = insts[k].n;
+    const long ro = insts[k].roff;
+    const PhotDev P = phot[insts[k].psr];
+    const dd tz = dd_make(ph_hi[ro + n], ph_lo[ro + n]);
+    double ac[MC], as[MC], sw[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < MC; j++) ac[j] = as[j] = 0.0;
+    for (int i = tid; i < n; i += PH_BT) {
+        const double phi = photon_phase(ph_hi, ph_lo, ro + i, P.abs_phase != 0, tz);
+        const double w = P.w ? P.w[i] : 1.0;
+        sw[0] += w;
+        sw[1] += w * w;
+        double c1, s1;
+        sincospi(2.0 * phi, &s1, &c1);
+        // e^{i 8 t} by three squarings
+        double c8 = c1, s8 = s1;
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const double c = c8 * c8 - s8 * s8, s = 2.0 * c8 * s8;
+            c8 = c, s8 = s;
+        }
+        double ca = 1.0, sa = 0.0;  // the anchor e^{i 8 b t}
+#pragma unroll
+        for (int b = 0; b < (MC + 7) / 8; b++) {
+            double c = ca, s = sa;
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                const int j = 8 * b + a;  // harmonic j + 1
+                if (j >= MC) break;
+                const double cn = c * c1 - s * s1, sn = c * s1 + s * c1;
+                c = cn, s = sn;
+                ac[j] = fma(w, c, ac[j]);
+                as[j] = fma(w, s, as[j]);
+            }
+            const double cn = ca * c8 - sa * s8, sn = ca * s8 + sa * c8;
+            ca = cn, sa = sn;
+        }
+    }
+    double* o = out + (long)k * (2 * m + 2);
+#pragma unroll
+    for (int g = 0; g < MC; g += 4) {  // four harmonics (eight sums) per barrier pair
+        double v[8];
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            v[2 * a] = g + a < MC ? ac[g + a] : 0.0;
+            v[2 * a + 1] = g + a < MC ? as[g + a] : 0.0;
+        }
+        block_sums<PH_BT / 64, 8>(v, sh);
+        if (tid == 0) {
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+                if (g + a < m) {
+                    o[2 * (g + a)] = v[2 * a];
+                    o[2 * (g + a) + 1] = v[2 * a + 1];
+                }
+        }
+    }
+    block_sums<PH_BT / 64, 2>(sw, sh);
+    if (tid == 0) {
+        o[2 * m] = sw[0];
+        o[2 * m + 1] = sw[1];
+    }
+}
+
 // Debug/parity introspection (pint_debug_gram): the assembled, unnormalised normal matrix
 // [M | r]^T N^-1 [M | r] of the last pint_fit_step in the original column order (the ECORR
 // block already eliminated by its Schur complement), (K+1)^2 per instance, followed by the K
@@ -6399,6 +6568,7 @@ struct pint_ctx {
     int cov_mode = 0;
     size_t cov_lds = 0;
     bool ic_valid = false;  // per-instance constants (k_prep) current for the tables
+    bool phases_valid = false;  // d_phhi / d_phlo hold pint_eval's phases of the current tables (the photon passes)
     bool no_events = false; // PINT_NO_EVENTS=1: no per-kernel timing events (their cost)
     int timing_mask = 0xff; // PINT_OPT_TIMING_MASK: timing slots whose events are recorded
     int timing_every = 1;   // PINT_OPT_TIMING_EVERY: Gram events on every k-th fit step
@@ -6490,6 +6660,12 @@ struct pint_ctx {
     size_t pl_cap = 0;
     double* d_pg = nullptr;  // pint_point_lnlike_gls scratch (class, epoch and Fourier values, offsets, outputs)
     size_t pg_cap = 0;
+    std::vector<PhotDev> phot;  // pint_set_photons: per pulsar (grown on demand; device buffers owned here)
+    PhotDev* d_phot = nullptr;  // their device copy, rebuilt when phot_dirty
+    int nphot_dev = 0;
+    bool phot_dirty = false;
+    double* d_pp = nullptr;  // pint_point_photon_lnlike / _trig scratch (offsets, outputs)
+    size_t pp_cap = 0;
     int n_plgls = 0;         // k_point_lnl_gls launches of this context (PINT_QUERY_NPLGLS)
     int n_batch_reuse = 0;   // pint_set_grid / pint_set_points calls that kept the resident batch (PINT_QUERY_NREUSE)
     double* d_noise = nullptr;  // pint_noise_resids: red and ECORR realisations (2 tot_out)
@@ -7133,6 +7309,12 @@ void pint_ctx_destroy(pint_ctx* ctx) {
     if (ctx->d_nz) hipFree(ctx->d_nz);
     if (ctx->d_pl) hipFree(ctx->d_pl);
     if (ctx->d_pg) hipFree(ctx->d_pg);
+    for (auto& p : ctx->phot) {
+        if (p.w) hipFree((void*)p.w);
+        if (p.tmpl) hipFree((void*)p.tmpl);
+    }
+    if (ctx->d_phot) hipFree(ctx->d_phot);
+    if (ctx->d_pp) hipFree(ctx->d_pp);
     if (ctx->d_status_slots) hipFree(ctx->d_status_slots);
     if (ctx->h_status) hipHostFree(ctx->h_status);
     for (int sl = 0; sl < pint_ctx::NSLOT; sl++) {
@@ -7798,6 +7980,7 @@ static int grid_batch(pint_ctx* ctx, int psr, int npts) {
         dfree((void*&)ctx->d_tables0);  // (a snapshot of the previous points)
         ctx->tables0_cap = 0;
         ctx->ic_valid = ctx->ic0_valid = false;
+        ctx->phases_valid = false;
         ctx->restore_pending = ctx->chi2_pending = ctx->cov_pending = false;
         ctx->wtile_valid = false;
         ctx->chi2_dst = nullptr;
@@ -8011,6 +8194,7 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
     ctx->nsplit = nsplit;
     ctx->red_valid[0] = ctx->red_valid[1] = 0;
     ctx->ic_valid = false;
+    ctx->phases_valid = false;
     // vg compact path (k_gram_v): contiguous DMX bins, no ECORR, nred <= 31, <= 47
     // timing columns; the DMX slots fill the [T | r] row tiles (+16 if needed) such that the
     // bins of every N-split are distinct mod vns; LDS width <= VMAXKP
@@ -8452,6 +8636,7 @@ int pint_get_tables(pint_ctx* ctx, double* out) {
 
 int pint_set_tables(pint_ctx* ctx, const double* tables) {
     ctx->ic_valid = false;
+    ctx->phases_valid = false;
     ctx->tables_fresh = false;
     ctx->restore_pending = false;  // overwritten anyway
     if (ctx->sigma_pending) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));  // k_sigma reads F0
@@ -8605,6 +8790,7 @@ int pint_eval(pint_ctx* ctx, int want_M) {
         }
     }
     record(ctx, want_M ? 2 : 0);
+    ctx->phases_valid = true;  // (enqueued below, on the stream the photon passes run on)
     const double* tabs = ctx->d_tables;
     const InstConst* icp = ctx->d_ic;
     EvalRestore rs{nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -9440,6 +9626,7 @@ int pint_apply_step(pint_ctx* ctx, const double* lambda_) {
     launch_apply(ctx, ctx->d_lam, 0.0);
     HIPCHK(hipGetLastError());
     ctx->ic_valid = true;
+    ctx->phases_valid = false;
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }
@@ -9453,6 +9640,7 @@ int pint_apply_step_uniform(pint_ctx* ctx, double lambda_) {
     launch_apply(ctx, nullptr, lambda_);
     HIPCHK(hipGetLastError());
     ctx->ic_valid = true;
+    ctx->phases_valid = false;
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }
@@ -9473,6 +9661,7 @@ int pint_fit_step_apply(pint_ctx* ctx, int mode, double lambda_) {
     if (ctx->apply_done) {
         ctx->apply_done = false;
         ctx->ic_valid = true;
+        ctx->phases_valid = false;
         return PINT_OK;
     }
     return pint_apply_step_uniform(ctx, lambda_);
@@ -9507,6 +9696,7 @@ int pint_restore_tables(pint_ctx* ctx) {
         return PINT_E_INVALID;
     }
     ctx->ic_valid = false;
+    ctx->phases_valid = false;
     ctx->tables_fresh = false;
     if (ctx->sigma_pending) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));  // k_sigma reads F0
     // deferred: the next pint_eval's k_prep copies the snapshot back as it forms the
@@ -10429,6 +10619,146 @@ int pint_point_lnlike_gls(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf,
     HIPCHK(hipGetLastError());
     ctx->n_plgls++;
     HIPCHK(d2h(out, d_out, sizeof(double) * 4 * ni, ctx->stream));
+    if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+int pint_set_photons(pint_ctx* ctx, int psr, int abs_phase, const double* weights, int nbin, const double* tmpl) {
+    if (!ctx) return PINT_E_INVALID;
+    if (psr < 0 || psr >= (int)ctx->psrs.size()) { ctx->err = "pint_set_photons: no such pulsar"; return PINT_E_INVALID; }
+    if (abs_phase != 0 && abs_phase != 1) { ctx->err = "pint_set_photons: abs_phase must be 0 or 1"; return PINT_E_INVALID; }
+    if (tmpl ? (nbin < 1 || nbin > PINT_MAX_TEMPLATE) : nbin != 0) {
+        ctx->err = "pint_set_photons: " + std::to_string(nbin) + " template bins (1.." + std::to_string(PINT_MAX_TEMPLATE) +
+                   " with a template, 0 without)";
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    const size_t n = (size_t)ctx->psrs[psr].n;
+    // the new copies first: a failure leaves the pulsar as it was
+    void *dw = nullptr, *dt = nullptr;
+    auto put = [&](const double* src, size_t count, void*& dst) {
+        if (!src) return hipSuccess;
+        hipError_t e = hipMalloc(&dst, sizeof(double) * std::max<size_t>(count, 1));
+        if (e == hipSuccess && count) e = h2d(dst, src, sizeof(double) * count, nullptr, true);
+        return e;
+    };
+    hipError_t e = put(weights, n, dw);
+    if (e == hipSuccess) e = put(tmpl, (size_t)nbin, dt);
+    if (e != hipSuccess) {
+        if (dw) hipFree(dw);
+        if (dt) hipFree(dt);
+        ctx->err = std::string("pint_set_photons: ") + hipGetErrorString(e);
+        return PINT_E_HIP;
+    }
+    if (ctx->phot.size() < ctx->psrs.size()) ctx->phot.resize(ctx->psrs.size(), PhotDev{nullptr, nullptr, 0, 0, 0, 0.0});
+    PhotDev& P = ctx->phot[psr];
+    if (P.w || P.tmpl) {
+        hipStreamSynchronize(ctx->stream);  // (a lazy call's kernel may still read the old copies)
+        if (P.w) hipFree((void*)P.w);
+        if (P.tmpl) hipFree((void*)P.tmpl);
+    }
+    P.w = (const double*)dw;
+    P.tmpl = (const double*)dt;
+    P.nbin = nbin;
+    P.has = 1;
+    P.abs_phase = abs_phase;
+    P.edge = nbin > 0 ? (double)(nbin - 1) * 1.0 / (double)nbin : 0.0;
+    ctx->phot_dirty = true;
+    return PINT_OK;
+}
+
+// the batch's pulsars all have photon data (and a template): checked before any launch; then the
+// device copy of the descriptors is brought up to date
+static int photon_ready(pint_ctx* ctx, const char* who, bool need_tmpl) {
+    for (int pi : ctx->upsr) {
+        const bool has = pi < (int)ctx->phot.size() && ctx->phot[pi].has;
+        if (!has || (need_tmpl && !ctx->phot[pi].tmpl)) {
+            ctx->err = std::string(who) + ": pulsar " + std::to_string(pi) + " of the batch has no " +
+                       (has ? "template" : "photon data") + " (pint_set_photons)";
+            return PINT_E_INVALID;
+        }
+    }
+    hipSetDevice(ctx->device);
+    if (ctx->phot.size() < ctx->psrs.size()) {
+        ctx->phot.resize(ctx->psrs.size(), PhotDev{nullptr, nullptr, 0, 0, 0, 0.0});
+        ctx->phot_dirty = true;
+    }
+    if (ctx->phot_dirty || ctx->nphot_dev != (int)ctx->phot.size()) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (ctx->d_phot) hipFree(ctx->d_phot);
+        ctx->d_phot = nullptr;
+        ctx->nphot_dev = 0;
+        HIPCHK(hipMalloc(&ctx->d_phot, sizeof(PhotDev) * ctx->phot.size()));
+        HIPCHK(h2d(ctx->d_phot, ctx->phot.data(), sizeof(PhotDev) * ctx->phot.size(), nullptr, true));
+        ctx->nphot_dev = (int)ctx->phot.size();
+        ctx->phot_dirty = false;
+    }
+    return PINT_OK;
+}
+
+static int photon_scratch(pint_ctx* ctx, size_t need) {
+    if (need > ctx->pp_cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a lazy call's kernel may still read the old one)
+        if (ctx->d_pp) hipFree(ctx->d_pp);
+        ctx->d_pp = nullptr;
+        ctx->pp_cap = 0;
+        HIPCHK(hipMalloc(&ctx->d_pp, sizeof(double) * need));
+        ctx->pp_cap = need;
+    }
+    return PINT_OK;
+}
+
+int pint_point_photon_lnlike(pint_ctx* ctx, int nphs, const double* phs, double* out) {
+    if (!ctx) return PINT_E_INVALID;
+    if (ctx->ninst <= 0 || !ctx->phases_valid || !ctx->d_phhi || !phs || !out) {
+        ctx->err = "pint_point_photon_lnlike: no evaluated batch (pint_eval after the last change of the tables), or a null array";
+        return PINT_E_INVALID;
+    }
+    if (nphs < 1 || nphs > PINT_MAX_PHOTON_PHS) {
+        ctx->err = "pint_point_photon_lnlike: " + std::to_string(nphs) + " phase offsets per instance (1.." +
+                   std::to_string(PINT_MAX_PHOTON_PHS) + ")";
+        return PINT_E_INVALID;
+    }
+    if (int rc = photon_ready(ctx, "pint_point_photon_lnlike", true)) return rc;
+    const int ni = ctx->ninst;
+    const size_t tot = (size_t)ni * nphs;
+    if (int rc = photon_scratch(ctx, 2 * tot)) return rc;
+    double* d_phs = ctx->d_pp;
+    double* d_out = d_phs + tot;
+    HIPCHK(h2d(d_phs, phs, sizeof(double) * tot, ctx->stream, false));
+    hipLaunchKernelGGL(k_photon_lnl, dim3(ni, (nphs + PH_J - 1) / PH_J), dim3(PH_BT), 0, ctx->stream, ctx->d_inst,
+                       ctx->d_phot, ctx->d_phhi, ctx->d_phlo, nphs, d_phs, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(out, d_out, sizeof(double) * tot, ctx->stream));
+    if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+int pint_point_photon_trig(pint_ctx* ctx, int m, double* out) {
+    if (!ctx) return PINT_E_INVALID;
+    if (ctx->ninst <= 0 || !ctx->phases_valid || !ctx->d_phhi || !out) {
+        ctx->err = "pint_point_photon_trig: no evaluated batch (pint_eval after the last change of the tables), or a null array";
+        return PINT_E_INVALID;
+    }
+    if (m < 1 || m > PINT_MAX_PHOTON_HARM) {
+        ctx->err = "pint_point_photon_trig: " + std::to_string(m) + " harmonics (1.." + std::to_string(PINT_MAX_PHOTON_HARM) + ")";
+        return PINT_E_INVALID;
+    }
+    if (int rc = photon_ready(ctx, "pint_point_photon_trig", false)) return rc;
+    const int ni = ctx->ninst;
+    const size_t tot = (size_t)ni * (2 * m + 2);
+    if (int rc = photon_scratch(ctx, tot)) return rc;
+    double* d_out = ctx->d_pp;
+#define PINT_PT_ARGS ctx->d_inst, ctx->d_phot, ctx->d_phhi, ctx->d_phlo, m, d_out
+    if (m <= 8)
+        hipLaunchKernelGGL(k_photon_trig<8>, dim3(ni), dim3(PH_BT), 0, ctx->stream, PINT_PT_ARGS);
+    else if (m <= 24)
+        hipLaunchKernelGGL(k_photon_trig<24>, dim3(ni), dim3(PH_BT), 0, ctx->stream, PINT_PT_ARGS);
+    else
+        hipLaunchKernelGGL(k_photon_trig<PINT_MAX_PHOTON_HARM>, dim3(ni), dim3(PH_BT), 0, ctx->stream, PINT_PT_ARGS);
+#undef PINT_PT_ARGS
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(out, d_out, sizeof(double) * tot, ctx->stream));
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }

@@ -1492,6 +1492,47 @@ class Session:
             self._keep += [q, e, p]
         return out.reshape(ni, 4)
 
+    def set_photons(self, lay, weights=None, template=None, abs_phase=True):
+        """The pulsar's rows as photons (pint_set_photons): weights (n, or None for unweighted data),
+        template (its values at the phases j / len(template), or None: only the trig sums), and
+        whether the photon phase is taken relative to the TZR row (model.phase's abs_phase).  A
+        second call replaces the data; a refused call leaves the previous data in force."""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        t = None if template is None else np.ascontiguousarray(template, dtype=np.float64)
+        if w is not None and w.shape != (lay.n,):
+            raise ValueError(f"weights must have {lay.n} entries, got {w.shape}")
+        if t is not None and t.ndim != 1:
+            raise ValueError("the template must be one-dimensional")
+        self._check(self.L.pint_set_photons(self.ctx, lay.psr_id, 1 if abs_phase else 0, L.ptr(w),
+                                            0 if t is None else t.size, L.ptr(t)))
+
+    def point_photon_lnlike(self, phs):
+        """k_photon_lnl over the batch, after eval(False): phs (ninst, nphs) phase offsets (or (ninst,):
+        one per instance) -> (ninst, nphs) sum_i log(w_i T((phi_i + phs) mod 1) + 1 - w_i) -- see
+        include/pint_amd.h pint_point_photon_lnlike.  Lazy: a pinned buffer, complete after check()."""
+        ni = len(self.inst_layout)
+        p = np.ascontiguousarray(phs, dtype=np.float64)
+        if p.ndim == 1:
+            p = p[:, None]
+        if p.ndim != 2 or p.shape[0] != ni:
+            raise ValueError(f"phs must be ({ni}, nphs), got {p.shape}")
+        p = np.ascontiguousarray(p)
+        out = self._pin("ptphl", p.size) if self.lazy else np.empty(p.size)
+        self._check(self.L.pint_point_photon_lnlike(self.ctx, p.shape[1], L.ptr(p), L.ptr(out)))
+        if self.lazy:
+            self._keep.append(p)
+        return out.reshape(p.shape)
+
+    def point_photon_trig(self, m=20):
+        """k_photon_trig over the batch, after eval(False): (ninst, 2 m + 2) = C_1, S_1, ..., C_m, S_m,
+        sum w, sum w^2 with C_j, S_j = sum_i w_i (cos, sin)(2 pi j phi_i) -- see include/pint_amd.h
+        pint_point_photon_trig.  Lazy: a pinned buffer, complete after check()."""
+        ni, m = len(self.inst_layout), int(m)
+        size = ni * (2 * max(m, 0) + 2)
+        out = self._pin("ptpht", size) if self.lazy else np.empty(size)
+        self._check(self.L.pint_point_photon_trig(self.ctx, m, L.ptr(out)))
+        return out.reshape(ni, 2 * m + 2)
+
     def debug_set_resids(self, resids):
         """Replace every instance's time residuals (list of n-arrays, seconds)."""
         flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64) for r in resids]))
