@@ -880,6 +880,63 @@ int pint_set_photons(pint_ctx *ctx, int psr, int abs_phase, const double *weight
 int pint_point_photon_lnlike(pint_ctx *ctx, int nphs, const double *phs, double *out);
 int pint_point_photon_trig(pint_ctx *ctx, int m, double *out);
 
+/* ---- polycos (polycos.py; reference src/pint/polycos.py) --------------------------------------
+ * tempo's piecewise polynomial phase predictor.  An entry (tmid, span, rphase, f0, coeffs) gives, with
+ * dt = (t - tmid) 1440 minutes,
+ *   phase(t) = rphase + 60 f0 dt + sum_i coeffs[i] dt^i,
+ *   freq(t)  = f0 + (sum_i i coeffs[i] dt^(i-1)) / 60,   fdot(t) = (sum_i i (i-1) coeffs[i] dt^(i-2)) / 3600.
+ * Every value that the reference keeps in longdouble crosses this interface as a (hi, lo) pair of
+ * doubles with hi = (double)v, lo = (double)(v - hi), and the device works on pairs in double-double.
+ * All five calls return when their outputs are complete (they synchronise, lazy mode or not).
+ *
+ * pint_polyco_fit: after pint_eval(ctx, 0), on instance inst whose rows are, per segment, nnode node
+ * rows then the segment's mid-point row (so n = nseg (nnode + 1)), the TZR row last.  Per segment:
+ *   rphase = phi(mid) - phi(TZR), split into an integer and a fraction in [-1/2, 1/2) (a pair);
+ *   y_j = (phi(node_j) - phi(mid)) - 60 F0 dt_j in double-double, rounded to a double, with
+ *         dt_j = dt_hi[s nnode + j] + dt_lo[...] minutes and F0 = f0_hi + f0_lo;
+ *   coeffs[s ncoeff + i]: the least-squares polynomial of degree ncoeff - 1 through (dt_hi_j, y_j), by
+ *         Householder QR of the Vandermonde matrix in dt / max |dt| (not by normal equations);
+ *   rms[s]: the root mean square of the nnode residuals of that fit (cycles).
+ * An output pointer may be NULL (not read back).  The result also stays on the device for
+ * pint_set_polycos to adopt.  1 <= ncoeff <= PINT_MAX_POLYCO_COEFF, ncoeff <= nnode <=
+ * PINT_MAX_POLYCO_NODES, else PINT_E_INVALID with a message before any launch; so for a batch that
+ * was not evaluated or an instance of another row count.
+ * pint_polyco_fit_host: the same kernel on phases given as host arrays of pairs, nseg (nnode + 1) + 1
+ * rows in that order (the TZR row last).
+ *
+ * pint_set_polycos: the table used by the two calls below, nent entries sorted by t_start
+ * (PINT_E_INVALID otherwise), ncoeff coefficients each (an entry with fewer: padded with zeros).
+ * hdr: PINT_PC_NF fields of nent doubles each, field-major, in the order tmid hi, lo; t_start hi, lo;
+ * t_stop hi, lo; rphase integer; rphase fraction hi, lo; f0 hi, lo.  c_hi, c_lo: nent x ncoeff.  Both
+ * NULL: the coefficients and rphase of the last pint_polyco_fit are adopted on the device (nent and
+ * ncoeff must be that fit's; the rphase fields of hdr are ignored).  A refused call leaves the previous
+ * table in force.
+ *
+ * pint_polyco_eval: n times as pairs.  The entry of a time is found as the reference's find_entry does
+ * (count(t_start < t) - 1 == count(t_stop < t), compared exactly on pairs: a time on a boundary
+ * belongs to the earlier entry).  want: bit 0 the absolute phase as out_int (an integer as a double)
+ * and out_frac (in [-1/2, 1/2)), bit 1 out_freq (Hz), bit 2 out_fdot (Hz/s); arrays not asked for may
+ * be NULL.  A time that no entry covers gets NaN in every output and is counted in *n_uncovered.
+ *
+ * pint_polyco_trig: C_1, S_1, ..., C_m, S_m, sum w, sum w^2 of the polyco phases of the n times (w: n
+ * weights or NULL), m in 1..PINT_MAX_PHOTON_HARM, in the layout of pint_point_photon_trig.  Computed
+ * by a grid whose size depends on n only, each workgroup's partial sums added in index order: the
+ * output's bits depend on the inputs only.  Uncovered times add nothing and are counted. */
+#define PINT_MAX_POLYCO_COEFF 16
+#define PINT_MAX_POLYCO_NODES 64
+#define PINT_PC_NF 11
+int pint_polyco_fit(pint_ctx *ctx, int inst, int nseg, int nnode, int ncoeff, const double *dt_hi, const double *dt_lo,
+                    double f0_hi, double f0_lo, double *coeffs, double *rph_int, double *rph_frac_hi,
+                    double *rph_frac_lo, double *rms);
+int pint_polyco_fit_host(pint_ctx *ctx, int nseg, int nnode, int ncoeff, const double *ph_hi, const double *ph_lo,
+                         const double *dt_hi, const double *dt_lo, double f0_hi, double f0_lo, double *coeffs,
+                         double *rph_int, double *rph_frac_hi, double *rph_frac_lo, double *rms);
+int pint_set_polycos(pint_ctx *ctx, int nent, int ncoeff, const double *hdr, const double *c_hi, const double *c_lo);
+int pint_polyco_eval(pint_ctx *ctx, int64_t n, const double *t_hi, const double *t_lo, int want, double *out_int,
+                     double *out_frac, double *out_freq, double *out_fdot, int64_t *n_uncovered);
+int pint_polyco_trig(pint_ctx *ctx, int64_t n, const double *t_hi, const double *t_lo, const double *w, int m,
+                     double *out, int64_t *n_uncovered);
+
 #ifdef __cplusplus
 }
 #endif

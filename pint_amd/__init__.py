@@ -7,7 +7,7 @@ DownhillWLSFitter / DownhillGLSFitter / Fitter.auto (fitter.py), grid_chisq
 ctypes C-ABI (include/pint_amd.h); there is no CPU fallback.
 """
 from .timing_model import TimingModel, get_model  # noqa: F401
-from .toa import TOAs, get_TOAs, get_model_and_toas  # noqa: F401
+from .toa import TOAs, get_TOAs, get_TOAs_array, get_model_and_toas  # noqa: F401
 from .residuals import Residuals, WidebandDMResiduals, WidebandTOAResiduals  # noqa: F401
 from .fitter import (Fitter, WLSFitter, GLSFitter, DownhillWLSFitter, DownhillGLSFitter, WidebandTOAFitter,  # noqa: F401
                      WidebandDownhillFitter,  # noqa: F401
@@ -31,7 +31,10 @@ def __getattr__(name):
     if name == "get_event_TOAs":
         from .event_toas import get_event_TOAs
         return get_event_TOAs
-    if name in ("eventstats", "event_optimize", "event_toas"):
+    if name in ("Polycos", "PolycoEntry"):
+        from . import polycos
+        return getattr(polycos, name)
+    if name in ("eventstats", "event_optimize", "event_toas", "polycos"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

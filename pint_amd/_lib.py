@@ -35,6 +35,9 @@ MAX_IFUNC = 1024  # PINT_MAX_IFUNC: IFunc control points
 MAX_TEMPLATE = 4096     # PINT_MAX_TEMPLATE: photon template bins
 MAX_PHOTON_PHS = 1024   # PINT_MAX_PHOTON_PHS: phase offsets per instance and call
 MAX_PHOTON_HARM = 64    # PINT_MAX_PHOTON_HARM: harmonics of the photon trig sums
+MAX_POLYCO_COEFF = 16   # PINT_MAX_POLYCO_COEFF
+MAX_POLYCO_NODES = 64   # PINT_MAX_POLYCO_NODES
+PC_NF = 11              # PINT_PC_NF: header fields of a polyco entry (pint_set_polycos)
 
 PINT_OK, PINT_E_INVALID, PINT_E_HIP, PINT_E_NOT_PD, PINT_E_KEPLER, PINT_E_PARAM, PINT_E_SIGMA = range(7)
 
@@ -216,6 +219,12 @@ def lib():
     L.pint_set_photons.argtypes = [vp, C.c_int, C.c_int, dptr, C.c_int, dptr]
     L.pint_point_photon_lnlike.argtypes = [vp, C.c_int, dptr, dptr]
     L.pint_point_photon_trig.argtypes = [vp, C.c_int, dptr]
+    i64p = C.POINTER(C.c_int64)
+    L.pint_polyco_fit.argtypes = [vp] + [C.c_int] * 4 + [dptr, dptr, C.c_double, C.c_double] + [dptr] * 5
+    L.pint_polyco_fit_host.argtypes = [vp] + [C.c_int] * 3 + [dptr] * 4 + [C.c_double, C.c_double] + [dptr] * 5
+    L.pint_set_polycos.argtypes = [vp, C.c_int, C.c_int, dptr, dptr, dptr]
+    L.pint_polyco_eval.argtypes = [vp, C.c_int64, dptr, dptr, C.c_int] + [dptr] * 4 + [i64p]
+    L.pint_polyco_trig.argtypes = [vp, C.c_int64, dptr, dptr, dptr, C.c_int, dptr, i64p]
     _lib = L
     L.pint_set_wideband.argtypes = [vp, C.c_int, dptr, dptr, dptr, C.POINTER(C.c_uint64)]
     L.pint_dm_resids.argtypes = [vp, C.c_int, C.c_int, dptr, dptr]
@@ -236,7 +245,8 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_fit_step_enqueue", "pint_set_grid", "pint_add_pulsar_cols", "pint_pack_toas",
             "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms",
             "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike", "pint_point_lnlike_gls",
-            "pint_set_photons", "pint_point_photon_lnlike", "pint_point_photon_trig"]
+            "pint_set_photons", "pint_point_photon_lnlike", "pint_point_photon_trig",
+            "pint_polyco_fit", "pint_polyco_fit_host", "pint_set_polycos", "pint_polyco_eval", "pint_polyco_trig"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

@@ -6280,6 +6280,304 @@ __global__ __launch_bounds__(PH_BT) void k_photon_trig(const InstDev* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------------
+// polycos (pint_set_polycos, pint_polyco_fit / _eval / _trig): tempo's piecewise polynomial
+// phase predictor, fitted to the evaluation's phases and evaluated at arbitrary times
+// ---------------------------------------------------------------------------------
+// The table on the device (pint_set_polycos), nent entries sorted by t_start: PC_NF fields of nent
+// doubles each, field-major, then the coefficients as nent x nc high parts and nent x nc low parts
+// (entries of fewer coefficients padded with zeros, which Horner passes through exactly).
+enum { PC_TMID_HI, PC_TMID_LO, PC_TS_HI, PC_TS_LO, PC_TE_HI, PC_TE_LO, PC_RINT, PC_RF_HI, PC_RF_LO, PC_F0_HI, PC_F0_LO, PC_NF };
+struct PolyDev {
+    const double* hdr;  // PC_NF x nent
+    const double* chi;  // nent x nc
+    const double* clo;
+    int nent, nc;
+};
+static_assert(PC_NF == PINT_PC_NF, "the header's field count");
+constexpr int PC_BT = 256;
+constexpr int PC_MAXG = 1024;  // workgroups of the sums' grid (the partials' row count)
+
+// a < b for normalised pairs (|lo| <= ulp(hi) / 2: the order of the values is the order of (hi, lo))
+__device__ __forceinline__ bool pair_lt(double ah, double al, double bh, double bl) {
+    return ah < bh || (ah == bh && al < bl);
+}
+// the number of entries of the sorted pair column (hi, lo) that are < t (np.searchsorted, side left)
+__device__ __forceinline__ int pair_count_lt(const double* __restrict__ hi, const double* __restrict__ lo, int n, double th,
+                                             double tl) {
+    int a = 0, b = n;  // entries [0, a) are < t, entries [b, n) are not
+    while (a < b) {
+        const int c = (a + b) >> 1;
+        if (pair_lt(hi[c], lo[c], th, tl)) a = c + 1; else b = c;
+    }
+    return a;
+}
+// the entry of time t (find_entry: count(t_start < t) - 1 == count(t_stop < t), so a time on a
+// boundary belongs to the earlier entry), or -1 when no entry covers it (or t is NaN)
+__device__ __forceinline__ int polyco_entry(const PolyDev T, double th, double tl) {
+    const double* H = T.hdr;
+    const int E = T.nent;
+    const int s = pair_count_lt(H + PC_TS_HI * E, H + PC_TS_LO * E, E, th, tl) - 1;
+    const int e = pair_count_lt(H + PC_TE_HI * E, H + PC_TE_LO * E, E, th, tl);
+    return (s == e && s >= 0 && th == th) ? s : -1;
+}
+// dt = (t - tmid) 1440 minutes in double-double
+__device__ __forceinline__ dd polyco_dt(const PolyDev T, int e, double th, double tl) {
+    const double* H = T.hdr;
+    const int E = T.nent;
+    const dd d = dd_add(two_sum(th, -H[PC_TMID_HI * E + e]), two_sum(tl, -H[PC_TMID_LO * E + e]));
+    return dd_mul_d(d, 1440.0);
+}
+// the absolute phase of entry e at dt, split once: rph_int + round(s) as a double, s - round(s) in
+// [-1/2, 1/2) rounded to a double, s = coeffs(dt) + rph_frac + 60 f0 dt in double-double
+__device__ __forceinline__ void polyco_phase(const PolyDev T, int e, dd dt, double* pint_, double* pfrac) {
+    const double* H = T.hdr;
+    const int E = T.nent, nc = T.nc;
+    const double* ch = T.chi + (long)e * nc;
+    const double* cl = T.clo + (long)e * nc;
+    dd p = dd_make(ch[nc - 1], cl[nc - 1]);
+    for (int i = nc - 2; i >= 0; i--) p = dd_add(dd_mul(p, dt), dd_make(ch[i], cl[i]));
+    const dd f0 = dd_make(H[PC_F0_HI * E + e], H[PC_F0_LO * E + e]);
+    dd s = dd_add(p, dd_mul(dd_mul_d(f0, 60.0), dt));
+    s = dd_add(s, dd_make(H[PC_RF_HI * E + e], H[PC_RF_LO * E + e]));
+    const dd r = dd_round_half_up(s);
+    double f = dd_to_d(dd_sub(s, r));
+    double k = dd_to_d(r);
+    if (f >= 0.5) {  // (a fraction within half an ulp of 1/2: the Phase convention keeps [-1/2, 1/2))
+        f -= 1.0;
+        k += 1.0;
+    }
+    *pint_ = H[PC_RINT * E + e] + k;
+    *pfrac = f;
+}
+
+// k_polyco_eval: one time per lane.  want bit 0: the absolute phase (integer, fraction), bit 1: the
+// frequency f0 + (sum i c_i dt^(i-1)) / 60, bit 2: its derivative (sum i (i-1) c_i dt^(i-2)) / 3600,
+// both by Horner in double-double and rounded once.  An uncovered time gets NaN and is counted.
+__global__ __launch_bounds__(PC_BT) void k_polyco_eval(PolyDev T, long n, const double* __restrict__ t_hi,
+                                                       const double* __restrict__ t_lo, int want, double* __restrict__ o_int,
+                                                       double* __restrict__ o_frac, double* __restrict__ o_freq,
+                                                       double* __restrict__ o_fdot, unsigned long long* __restrict__ nunc) {
+    const long i = (long)blockIdx.x * PC_BT + threadIdx.x;
+    if (i >= n) return;
+    const double th = t_hi[i], tl = t_lo[i];
+    const int e = polyco_entry(T, th, tl);
+    if (e < 0) {
+        const double nan = __builtin_nan("");
+        if (want & 1) o_int[i] = o_frac[i] = nan;
+        if (want & 2) o_freq[i] = nan;
+        if (want & 4) o_fdot[i] = nan;
+        atomicAdd(nunc, 1ULL);
+        return;
+    }
+    const dd dt = polyco_dt(T, e, th, tl);
+    if (want & 1) {
+        double k, f;
+        polyco_phase(T, e, dt, &k, &f);
+        o_int[i] = k;
+        o_frac[i] = f;
+    }
+    if (want & 6) {
+        const int nc = T.nc, E = T.nent;
+        const double* ch = T.chi + (long)e * nc;
+        const double* cl = T.clo + (long)e * nc;
+        dd p1 = dd_make(0.0), p2 = dd_make(0.0);
+        for (int q = nc - 1; q >= 1; q--) {
+            const dd c = dd_make(ch[q], cl[q]);
+            p1 = dd_add(dd_mul(p1, dt), dd_mul_d(c, (double)q));
+            if (q >= 2) p2 = dd_add(dd_mul(p2, dt), dd_mul_d(c, (double)(q * (q - 1))));
+        }
+        if (want & 2)
+            o_freq[i] = dd_to_d(dd_add(dd_make(T.hdr[PC_F0_HI * E + e], T.hdr[PC_F0_LO * E + e]), dd_div_d(p1, 60.0)));
+        if (want & 4) o_fdot[i] = dd_to_d(dd_div_d(p2, 3600.0));
+    }
+}
+
+// k_polyco_trig: the trigonometric sums (k_photon_trig's, its rotations copied so that its builds
+// stay as they are) of the polyco phases of n times, over a grid that depends on n only: workgroup b
+// takes the times b PC_BT + tid + q gridDim PC_BT, and leaves its 2 m + 2 sums (block_sums' order)
+// in part[b][...]; k_polyco_trig_reduce adds the rows in index order.  So a call's bits depend on n
+// and m only.  An uncovered time adds nothing and is counted.  Reads 16 B (24 B) per time.
+template <int MC>
+__global__ __launch_bounds__(PC_BT) void k_polyco_trig(PolyDev T, long n, const double* __restrict__ t_hi,
+                                                       const double* __restrict__ t_lo, const double* __restrict__ wt, int m,
+                                                       double* __restrict__ part, unsigned long long* __restrict__ nunc) {
+    __shared__ double sh[8 * (PC_BT / 64)];
+    const int tid = threadIdx.x;
+    double ac[MC], as[MC], sw[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < MC; j++) ac[j] = as[j] = 0.0;
+    const long stride = (long)gridDim.x * PC_BT;
+    for (long i = (long)blockIdx.x * PC_BT + tid; i < n; i += stride) {
+        const double th = t_hi[i], tl = t_lo[i];
+        const int e = polyco_entry(T, th, tl);
+        if (e < 0) {
+            atomicAdd(nunc, 1ULL);
+            continue;
+        }
+        double k, phi;
+        polyco_phase(T, e, polyco_dt(T, e, th, tl), &k, &phi);
+        const double w = wt ? wt[i] : 1.0;
+        sw[0] += w;
+        sw[1] += w * w;
+        double c1, s1;
+        sincospi(2.0 * phi, &s1, &c1);  // (phi in [-1/2, 1/2): the same angle as phi mod 1)
+        double c8 = c1, s8 = s1;        // e^{i 8 t} by three squarings
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const double c = c8 * c8 - s8 * s8, s = 2.0 * c8 * s8;
+            c8 = c, s8 = s;
+        }
+        double ca = 1.0, sa = 0.0;  // the anchor e^{i 8 b t}
+#pragma unroll
+        for (int b = 0; b < (MC + 7) / 8; b++) {
+            double c = ca, s = sa;
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                const int j = 8 * b + a;  // harmonic j + 1
+                if (j >= MC) break;
+                const double cn = c * c1 - s * s1, sn = c * s1 + s * c1;
+                c = cn, s = sn;
+                ac[j] = fma(w, c, ac[j]);
+                as[j] = fma(w, s, as[j]);
+            }
+            const double cn = ca * c8 - sa * s8, sn = ca * s8 + sa * c8;
+            ca = cn, sa = sn;
+        }
+    }
+    double* o = part + (long)blockIdx.x * (2 * m + 2);
+#pragma unroll
+    for (int g = 0; g < MC; g += 4) {  // four harmonics (eight sums) per barrier pair
+        double v[8];
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            v[2 * a] = g + a < MC ? ac[g + a] : 0.0;
+            v[2 * a + 1] = g + a < MC ? as[g + a] : 0.0;
+        }
+        block_sums<PC_BT / 64, 8>(v, sh);
+        if (tid == 0) {
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+                if (g + a < m) {
+                    o[2 * (g + a)] = v[2 * a];
+                    o[2 * (g + a) + 1] = v[2 * a + 1];
+                }
+        }
+    }
+    block_sums<PC_BT / 64, 2>(sw, sh);
+    if (tid == 0) {
+        o[2 * m] = sw[0];
+        o[2 * m + 1] = sw[1];
+    }
+}
+// out[q] = sum over the nb partial rows of part[b][q], b ascending: one thread per sum
+__global__ __launch_bounds__(256) void k_polyco_trig_reduce(const double* __restrict__ part, int nb, int nq,
+                                                            double* __restrict__ out) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    double t = 0.0;
+    for (int b = 0; b < nb; b++) t += part[(long)b * nq + q];
+    out[q] = t;
+}
+
+// k_polyco_fit: one wave per segment, lane j its node j (nnode <= 64).  The rows of a segment are
+// its nnode node phases then its mid-point's (pairs), row0 the first segment's first row, tz the TZR
+// row.  rphase = phi(mid) - phi(TZR) split as Phase does; y_j = (phi_j - phi(mid)) - 60 F0 dt_j formed
+// in double-double from the dt pairs and rounded once; then the least-squares polynomial of degree
+// nc - 1 in the float64 dt by Householder QR of the Vandermonde matrix in x = dt / max |dt| (its
+// columns in registers, one row per lane, every norm and dot product a wave reduction), back
+// substitution on every lane, and c_i = a_i / h^i.  No LDS, no atomics.  rms: the root mean square of
+// the node residuals, the norm of the rows of Q^T y below the triangle.
+constexpr int PF_MAXC = PINT_MAX_POLYCO_COEFF;
+__global__ __launch_bounds__(256) void k_polyco_fit(int nseg, int nnode, int nc, const double* __restrict__ ph_hi,
+                                                    const double* __restrict__ ph_lo, long row0, long tzrow,
+                                                    const double* __restrict__ dt_hi, const double* __restrict__ dt_lo,
+                                                    double f0_hi, double f0_lo, double* __restrict__ coeffs,
+                                                    double* __restrict__ rph /* int, frac hi, frac lo: nseg each */,
+                                                    double* __restrict__ rms) {
+    const int seg = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (seg >= nseg) return;  // (uniform over the wave)
+    const bool live = lane < nnode;
+    const long r0 = row0 + (long)seg * (nnode + 1);
+    const dd mid = dd_make(ph_hi[r0 + nnode], ph_lo[r0 + nnode]);
+    double x = 0.0, y = 0.0;
+    if (live) {
+        const long q = (long)seg * nnode + lane;
+        const dd dtp = dd_make(dt_hi[q], dt_lo[q]);
+        const dd d = dd_sub(dd_make(ph_hi[r0 + lane], ph_lo[r0 + lane]), mid);
+        y = dd_to_d(dd_sub(d, dd_mul(dd_mul_d(dd_make(f0_hi, f0_lo), 60.0), dtp)));
+        x = dt_hi[q];
+    }
+    double h = fabs(x);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) h = fmax(h, __shfl_xor(h, o, 64));
+    if (h == 0.0) h = 1.0;
+    x /= h;
+    double a[PF_MAXC], diag[PF_MAXC];
+    {
+        double p = live ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < PF_MAXC; k++) {
+            a[k] = k < nc ? p : 0.0;
+            diag[k] = 1.0;
+            p *= x;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PF_MAXC; k++) {
+        if (k >= nc) continue;  // (uniform over the grid)
+        const bool in = live && lane >= k;
+        double v = in ? a[k] : 0.0;
+        const double sigma = wave_sum(v * v);
+        const double akk = __shfl(a[k], k, 64);
+        const double alpha = akk > 0.0 ? -sqrt(sigma) : sqrt(sigma);
+        if (lane == k) v -= alpha;
+        const double vv = 2.0 * (sigma - alpha * akk);  // |v|^2
+        diag[k] = alpha;
+        if (vv > 0.0) {
+            const double g = 2.0 / vv;
+#pragma unroll
+            for (int j = k + 1; j < PF_MAXC; j++) {
+                if (j < nc) {
+                    const double dot = wave_sum(v * a[j]);
+                    a[j] -= g * dot * v;
+                }
+            }
+            const double dot = wave_sum(v * y);
+            y -= g * dot * v;
+        }
+    }
+    // R c = (Q^T y)[0 .. nc): row i of R sits on lane i (its diagonal in diag[i]); every lane solves
+    double c[PF_MAXC];
+#pragma unroll
+    for (int i = PF_MAXC - 1; i >= 0; i--) {
+        c[i] = 0.0;
+        if (i < nc) {
+            double s = __shfl(y, i, 64);
+#pragma unroll
+            for (int j = i + 1; j < PF_MAXC; j++)
+                if (j < nc) s -= __shfl(a[j], i, 64) * c[j];
+            c[i] = s / diag[i];
+        }
+    }
+    const double r2 = wave_sum((live && lane >= nc) ? y * y : 0.0);
+    if (lane == 0) {
+        double sc = 1.0;
+#pragma unroll
+        for (int i = 0; i < PF_MAXC; i++) {
+            if (i < nc) coeffs[(long)seg * nc + i] = c[i] / sc;
+            sc *= h;
+        }
+        const dd r = dd_sub(mid, dd_make(ph_hi[tzrow], ph_lo[tzrow]));
+        const dd ri = dd_round_half_up(r);
+        const dd rf = dd_sub(r, ri);
+        rph[seg] = dd_to_d(ri);
+        rph[nseg + seg] = rf.hi;
+        rph[2 * (long)nseg + seg] = rf.lo;
+        rms[seg] = sqrt(r2 / (double)nnode);
+    }
+}
+
 // Debug/parity introspection (pint_debug_gram): the assembled, unnormalised normal matrix
 // [M | r]^T N^-1 [M | r] of the last pint_fit_step in the original column order (the ECORR
 // block already eliminated by its Schur complement), (K+1)^2 per instance, followed by the K
@@ -6666,6 +6964,12 @@ struct pint_ctx {
     bool phot_dirty = false;
     double* d_pp = nullptr;  // pint_point_photon_lnlike / _trig scratch (offsets, outputs)
     size_t pp_cap = 0;
+    PolyDev poly{nullptr, nullptr, nullptr, 0, 0};  // pint_set_polycos: the table (one buffer, at poly.hdr)
+    double* d_pfit = nullptr;  // pint_polyco_fit's last result: coeffs (nseg x nc), rph (3 nseg), rms (nseg)
+    size_t pfit_cap = 0;
+    int pfit_nseg = 0, pfit_nc = 0;
+    double* d_pc = nullptr;    // pint_polyco_* scratch (times, weights, outputs, partials; the counter first)
+    size_t pc_cap = 0;
     int n_plgls = 0;         // k_point_lnl_gls launches of this context (PINT_QUERY_NPLGLS)
     int n_batch_reuse = 0;   // pint_set_grid / pint_set_points calls that kept the resident batch (PINT_QUERY_NREUSE)
     double* d_noise = nullptr;  // pint_noise_resids: red and ECORR realisations (2 tot_out)
@@ -7315,6 +7619,9 @@ void pint_ctx_destroy(pint_ctx* ctx) {
     }
     if (ctx->d_phot) hipFree(ctx->d_phot);
     if (ctx->d_pp) hipFree(ctx->d_pp);
+    if (ctx->poly.hdr) hipFree((void*)ctx->poly.hdr);
+    if (ctx->d_pfit) hipFree(ctx->d_pfit);
+    if (ctx->d_pc) hipFree(ctx->d_pc);
     if (ctx->d_status_slots) hipFree(ctx->d_status_slots);
     if (ctx->h_status) hipHostFree(ctx->h_status);
     for (int sl = 0; sl < pint_ctx::NSLOT; sl++) {
@@ -10760,6 +11067,249 @@ int pint_point_photon_trig(pint_ctx* ctx, int m, double* out) {
     HIPCHK(hipGetLastError());
     HIPCHK(d2h(out, d_out, sizeof(double) * tot, ctx->stream));
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+// ---- polycos ----
+static int polyco_scratch(pint_ctx* ctx, size_t need) {
+    if (need > ctx->pc_cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (ctx->d_pc) hipFree(ctx->d_pc);
+        ctx->d_pc = nullptr;
+        ctx->pc_cap = 0;
+        HIPCHK(hipMalloc(&ctx->d_pc, sizeof(double) * need));
+        ctx->pc_cap = need;
+    }
+    return PINT_OK;
+}
+
+// the fit of nseg segments whose phase rows start at row0 of (d_hi, d_lo), the TZR row at tzrow
+static int polyco_fit_impl(pint_ctx* ctx, int nseg, int nnode, int ncoeff, const double* d_hi,
+                           const double* d_lo, long row0, long tzrow, double* d_dt, double f0_hi, double f0_lo,
+                           double* coeffs, double* rph_int, double* rph_frac_hi, double* rph_frac_lo, double* rms) {
+    const size_t nco = (size_t)nseg * ncoeff, need = nco + 4 * (size_t)nseg;
+    if (need > ctx->pfit_cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (ctx->d_pfit) hipFree(ctx->d_pfit);
+        ctx->d_pfit = nullptr;
+        ctx->pfit_cap = 0;
+        ctx->pfit_nseg = 0;
+        HIPCHK(hipMalloc(&ctx->d_pfit, sizeof(double) * need));
+        ctx->pfit_cap = need;
+    }
+    double* d_c = ctx->d_pfit;
+    double* d_rph = d_c + nco;
+    double* d_rms = d_rph + 3 * (size_t)nseg;
+    const size_t nd = (size_t)nseg * nnode;
+    hipLaunchKernelGGL(k_polyco_fit, dim3((nseg + 3) / 4), dim3(256), 0, ctx->stream, nseg, nnode, ncoeff, d_hi, d_lo, row0,
+                       tzrow, d_dt, d_dt + nd, f0_hi, f0_lo, d_c, d_rph, d_rms);
+    HIPCHK(hipGetLastError());
+    ctx->pfit_nseg = nseg;
+    ctx->pfit_nc = ncoeff;
+    if (coeffs) HIPCHK(d2h(coeffs, d_c, sizeof(double) * nco, ctx->stream));
+    if (rph_int) HIPCHK(d2h(rph_int, d_rph, sizeof(double) * nseg, ctx->stream));
+    if (rph_frac_hi) HIPCHK(d2h(rph_frac_hi, d_rph + nseg, sizeof(double) * nseg, ctx->stream));
+    if (rph_frac_lo) HIPCHK(d2h(rph_frac_lo, d_rph + 2 * (size_t)nseg, sizeof(double) * nseg, ctx->stream));
+    if (rms) HIPCHK(d2h(rms, d_rms, sizeof(double) * nseg, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PINT_OK;
+}
+
+static int polyco_fit_args(pint_ctx* ctx, const char* who, int nseg, int nnode, int ncoeff, const double* dt_hi,
+                           const double* dt_lo) {
+    if (nseg < 1 || !dt_hi || !dt_lo) {
+        ctx->err = std::string(who) + ": no segments, or a null array";
+        return PINT_E_INVALID;
+    }
+    if (ncoeff < 1 || ncoeff > PINT_MAX_POLYCO_COEFF || nnode < ncoeff || nnode > PINT_MAX_POLYCO_NODES) {
+        ctx->err = std::string(who) + ": " + std::to_string(ncoeff) + " coefficients (1.." +
+                   std::to_string(PINT_MAX_POLYCO_COEFF) + ") on " + std::to_string(nnode) + " nodes (ncoeff.." +
+                   std::to_string(PINT_MAX_POLYCO_NODES) + ")";
+        return PINT_E_INVALID;
+    }
+    return PINT_OK;
+}
+
+int pint_polyco_fit(pint_ctx* ctx, int inst, int nseg, int nnode, int ncoeff, const double* dt_hi, const double* dt_lo,
+                    double f0_hi, double f0_lo, double* coeffs, double* rph_int, double* rph_frac_hi, double* rph_frac_lo,
+                    double* rms) {
+    if (!ctx) return PINT_E_INVALID;
+    if (int rc = polyco_fit_args(ctx, "pint_polyco_fit", nseg, nnode, ncoeff, dt_hi, dt_lo)) return rc;
+    if (ctx->ninst <= 0 || !ctx->phases_valid || !ctx->d_phhi || inst < 0 || inst >= ctx->ninst) {
+        ctx->err = "pint_polyco_fit: no evaluated batch (pint_eval after the last change of the tables), or no such instance";
+        return PINT_E_INVALID;
+    }
+    const InstDev& I = ctx->inst[inst];
+    if ((long)I.n != (long)nseg * (nnode + 1)) {
+        ctx->err = "pint_polyco_fit: the instance has " + std::to_string(I.n) + " rows, not nseg (nnode + 1) = " +
+                   std::to_string((long)nseg * (nnode + 1));
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    const size_t nd = (size_t)nseg * nnode;
+    if (int rc = polyco_scratch(ctx, 1 + 2 * nd)) return rc;
+    double* d_dt = ctx->d_pc + 1;
+    HIPCHK(h2d(d_dt, dt_hi, sizeof(double) * nd, ctx->stream, false));
+    HIPCHK(h2d(d_dt + nd, dt_lo, sizeof(double) * nd, ctx->stream, false));
+    return polyco_fit_impl(ctx, nseg, nnode, ncoeff, ctx->d_phhi, ctx->d_phlo, I.roff, I.roff + I.n, d_dt,
+                           f0_hi, f0_lo, coeffs, rph_int, rph_frac_hi, rph_frac_lo, rms);
+}
+
+int pint_polyco_fit_host(pint_ctx* ctx, int nseg, int nnode, int ncoeff, const double* ph_hi, const double* ph_lo,
+                         const double* dt_hi, const double* dt_lo, double f0_hi, double f0_lo, double* coeffs,
+                         double* rph_int, double* rph_frac_hi, double* rph_frac_lo, double* rms) {
+    if (!ctx) return PINT_E_INVALID;
+    if (int rc = polyco_fit_args(ctx, "pint_polyco_fit_host", nseg, nnode, ncoeff, dt_hi, dt_lo)) return rc;
+    if (!ph_hi || !ph_lo) {
+        ctx->err = "pint_polyco_fit_host: a null array";
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    const size_t nd = (size_t)nseg * nnode, nr = (size_t)nseg * (nnode + 1) + 1;
+    if (int rc = polyco_scratch(ctx, 1 + 2 * nd + 2 * nr)) return rc;
+    double* d_dt = ctx->d_pc + 1;
+    double* d_ph = d_dt + 2 * nd;
+    HIPCHK(h2d(d_dt, dt_hi, sizeof(double) * nd, ctx->stream, false));
+    HIPCHK(h2d(d_dt + nd, dt_lo, sizeof(double) * nd, ctx->stream, false));
+    HIPCHK(h2d(d_ph, ph_hi, sizeof(double) * nr, ctx->stream, false));
+    HIPCHK(h2d(d_ph + nr, ph_lo, sizeof(double) * nr, ctx->stream, false));
+    return polyco_fit_impl(ctx, nseg, nnode, ncoeff, d_ph, d_ph + nr, 0, (long)nr - 1, d_dt, f0_hi,
+                           f0_lo, coeffs, rph_int, rph_frac_hi, rph_frac_lo, rms);
+}
+
+int pint_set_polycos(pint_ctx* ctx, int nent, int ncoeff, const double* hdr, const double* c_hi, const double* c_lo) {
+    if (!ctx) return PINT_E_INVALID;
+    if (nent < 1 || ncoeff < 1 || ncoeff > PINT_MAX_POLYCO_COEFF || !hdr || (c_hi != nullptr) != (c_lo != nullptr)) {
+        ctx->err = "pint_set_polycos: " + std::to_string(nent) + " entries of " + std::to_string(ncoeff) +
+                   " coefficients (1.." + std::to_string(PINT_MAX_POLYCO_COEFF) + "), or a null array";
+        return PINT_E_INVALID;
+    }
+    const bool adopt = c_hi == nullptr;
+    if (adopt && (ctx->pfit_nseg != nent || ctx->pfit_nc != ncoeff)) {
+        ctx->err = "pint_set_polycos: no coefficients given and the last pint_polyco_fit left " +
+                   std::to_string(ctx->pfit_nseg) + " x " + std::to_string(ctx->pfit_nc) + ", not " + std::to_string(nent) +
+                   " x " + std::to_string(ncoeff);
+        return PINT_E_INVALID;
+    }
+    const double* ts = hdr + (size_t)PC_TS_HI * nent;
+    const double* tl = hdr + (size_t)PC_TS_LO * nent;
+    for (int e = 1; e < nent; e++)
+        if (ts[e] < ts[e - 1] || (ts[e] == ts[e - 1] && tl[e] < tl[e - 1])) {
+            ctx->err = "pint_set_polycos: the entries are not sorted by t_start";
+            return PINT_E_INVALID;
+        }
+    hipSetDevice(ctx->device);
+    const size_t nh = (size_t)PC_NF * nent, nco = (size_t)nent * ncoeff;
+    double* d = nullptr;
+    HIPCHK(hipMalloc(&d, sizeof(double) * (nh + 2 * nco)));
+    hipError_t e = h2d(d, hdr, sizeof(double) * nh, nullptr, true);
+    if (e == hipSuccess && !adopt) e = h2d(d + nh, c_hi, sizeof(double) * nco, nullptr, true);
+    if (e == hipSuccess && !adopt) e = h2d(d + nh + nco, c_lo, sizeof(double) * nco, nullptr, true);
+    if (e == hipSuccess && adopt) {  // the fit's coefficients (doubles) and rphase, device to device
+        const double* f = ctx->d_pfit;
+        e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(d + nh, f, sizeof(double) * nco, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemset(d + nh + nco, 0, sizeof(double) * nco);
+        if (e == hipSuccess)
+            e = hipMemcpy(d + (size_t)PC_RINT * nent, f + nco, sizeof(double) * 3 * nent, hipMemcpyDeviceToDevice);
+        static_assert(PC_RF_HI == PC_RINT + 1 && PC_RF_LO == PC_RINT + 2, "rph is (int, frac hi, frac lo), contiguous");
+    }
+    if (e != hipSuccess) {
+        hipFree(d);
+        ctx->err = std::string("pint_set_polycos: ") + hipGetErrorString(e);
+        return PINT_E_HIP;
+    }
+    if (ctx->poly.hdr) {
+        hipStreamSynchronize(ctx->stream);
+        hipFree((void*)ctx->poly.hdr);
+    }
+    ctx->poly = PolyDev{d, d + nh, d + nh + nco, nent, ncoeff};
+    return PINT_OK;
+}
+
+int pint_polyco_eval(pint_ctx* ctx, int64_t n, const double* t_hi, const double* t_lo, int want, double* out_int,
+                     double* out_frac, double* out_freq, double* out_fdot, int64_t* n_uncovered) {
+    if (!ctx) return PINT_E_INVALID;
+    if (!ctx->poly.hdr) {
+        ctx->err = "pint_polyco_eval: no polyco table (pint_set_polycos)";
+        return PINT_E_INVALID;
+    }
+    if (n < 1 || !t_hi || !t_lo || !n_uncovered || !(want & 7) || (want & ~7) || ((want & 1) && (!out_int || !out_frac)) ||
+        ((want & 2) && !out_freq) || ((want & 4) && !out_fdot)) {
+        ctx->err = "pint_polyco_eval: no times, no output asked for, or a null array";
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    const size_t N = (size_t)n;
+    if (int rc = polyco_scratch(ctx, 1 + 6 * N)) return rc;
+    unsigned long long* d_cnt = (unsigned long long*)ctx->d_pc;
+    static_assert(sizeof(unsigned long long) == sizeof(double), "the counter takes the scratch's first slot");
+    double* d_t = ctx->d_pc + 1;
+    double* d_o = d_t + 2 * N;
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(double), ctx->stream));
+    HIPCHK(h2d(d_t, t_hi, sizeof(double) * N, ctx->stream, false));
+    HIPCHK(h2d(d_t + N, t_lo, sizeof(double) * N, ctx->stream, false));
+    hipLaunchKernelGGL(k_polyco_eval, dim3((unsigned)((N + PC_BT - 1) / PC_BT)), dim3(PC_BT), 0, ctx->stream, ctx->poly,
+                       (long)n, d_t, d_t + N, want, d_o, d_o + N, d_o + 2 * N, d_o + 3 * N, d_cnt);
+    HIPCHK(hipGetLastError());
+    if (want & 1) {
+        HIPCHK(d2h(out_int, d_o, sizeof(double) * N, ctx->stream));
+        HIPCHK(d2h(out_frac, d_o + N, sizeof(double) * N, ctx->stream));
+    }
+    if (want & 2) HIPCHK(d2h(out_freq, d_o + 2 * N, sizeof(double) * N, ctx->stream));
+    if (want & 4) HIPCHK(d2h(out_fdot, d_o + 3 * N, sizeof(double) * N, ctx->stream));
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *n_uncovered = (int64_t)cnt;
+    return PINT_OK;
+}
+
+int pint_polyco_trig(pint_ctx* ctx, int64_t n, const double* t_hi, const double* t_lo, const double* w, int m, double* out,
+                     int64_t* n_uncovered) {
+    if (!ctx) return PINT_E_INVALID;
+    if (!ctx->poly.hdr) {
+        ctx->err = "pint_polyco_trig: no polyco table (pint_set_polycos)";
+        return PINT_E_INVALID;
+    }
+    if (n < 1 || !t_hi || !t_lo || !out || !n_uncovered) {
+        ctx->err = "pint_polyco_trig: no times, or a null array";
+        return PINT_E_INVALID;
+    }
+    if (m < 1 || m > PINT_MAX_PHOTON_HARM) {
+        ctx->err = "pint_polyco_trig: " + std::to_string(m) + " harmonics (1.." + std::to_string(PINT_MAX_PHOTON_HARM) + ")";
+        return PINT_E_INVALID;
+    }
+    hipSetDevice(ctx->device);
+    const size_t N = (size_t)n;
+    const int nq = 2 * m + 2;
+    const int nb = (int)std::min<size_t>((N + PC_BT - 1) / PC_BT, (size_t)PC_MAXG);  // (a function of n alone)
+    if (int rc = polyco_scratch(ctx, 1 + 3 * N + (size_t)(nb + 1) * nq)) return rc;
+    unsigned long long* d_cnt = (unsigned long long*)ctx->d_pc;
+    double* d_t = ctx->d_pc + 1;
+    double* d_w = d_t + 2 * N;
+    double* d_part = d_w + N;
+    double* d_out = d_part + (size_t)nb * nq;
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(double), ctx->stream));
+    HIPCHK(h2d(d_t, t_hi, sizeof(double) * N, ctx->stream, false));
+    HIPCHK(h2d(d_t + N, t_lo, sizeof(double) * N, ctx->stream, false));
+    if (w) HIPCHK(h2d(d_w, w, sizeof(double) * N, ctx->stream, false));
+#define PINT_PCT_ARGS ctx->poly, (long)n, d_t, d_t + N, w ? d_w : nullptr, m, d_part, d_cnt
+    if (m <= 8)
+        hipLaunchKernelGGL(k_polyco_trig<8>, dim3(nb), dim3(PC_BT), 0, ctx->stream, PINT_PCT_ARGS);
+    else if (m <= 24)
+        hipLaunchKernelGGL(k_polyco_trig<24>, dim3(nb), dim3(PC_BT), 0, ctx->stream, PINT_PCT_ARGS);
+    else
+        hipLaunchKernelGGL(k_polyco_trig<PINT_MAX_PHOTON_HARM>, dim3(nb), dim3(PC_BT), 0, ctx->stream, PINT_PCT_ARGS);
+#undef PINT_PCT_ARGS
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_polyco_trig_reduce, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, d_part, nb, nq, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(out, d_out, sizeof(double) * nq, ctx->stream));
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *n_uncovered = (int64_t)cnt;
     return PINT_OK;
 }
 

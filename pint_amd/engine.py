@@ -1533,6 +1533,87 @@ class Session:
         self._check(self.L.pint_point_photon_trig(self.ctx, m, L.ptr(out)))
         return out.reshape(ni, 2 * m + 2)
 
+    # -- polycos (include/pint_amd.h "polycos"; pint_amd/polycos.py) ---------------------------
+    def _polyco_fit_out(self, nseg, ncoeff):
+        return [np.empty(nseg * ncoeff)] + [np.empty(nseg) for _ in range(4)]
+
+    @staticmethod
+    def _polyco_fit_result(out, nseg, ncoeff):
+        co, ri, fh, fl, rms = out
+        return {"coeffs": co.reshape(nseg, ncoeff), "rph_int": ri, "rph_frac_hi": fh, "rph_frac_lo": fl, "rms": rms}
+
+    def polyco_fit(self, nseg, nnode, ncoeff, dt_hi, dt_lo, f0, inst=0):
+        """pint_polyco_fit on instance ``inst`` after eval(False): its rows are, per segment, nnode node
+        rows then the mid-point row.  dt_hi, dt_lo: (nseg, nnode) minutes as pairs; f0: longdouble.
+        -> dict of coeffs (nseg, ncoeff), rph_int, rph_frac_hi, rph_frac_lo, rms."""
+        dh = np.ascontiguousarray(dt_hi, dtype=np.float64).reshape(-1)
+        dl = np.ascontiguousarray(dt_lo, dtype=np.float64).reshape(-1)
+        if dh.size != nseg * nnode or dl.size != dh.size:
+            raise ValueError(f"dt must hold nseg x nnode = {nseg * nnode} values, got {dh.size} and {dl.size}")
+        out = self._polyco_fit_out(nseg, ncoeff) if 0 < nseg and 0 < ncoeff <= L.MAX_POLYCO_COEFF else [np.empty(1)] * 5
+        fh, fl = split_ld(f0)
+        self._check(self.L.pint_polyco_fit(self.ctx, inst, nseg, nnode, ncoeff, L.ptr(dh), L.ptr(dl), fh, fl,
+                                           *[L.ptr(o) for o in out]))
+        return self._polyco_fit_result(out, nseg, ncoeff)
+
+    def polyco_fit_host(self, nseg, nnode, ncoeff, ph_hi, ph_lo, dt_hi, dt_lo, f0):
+        """pint_polyco_fit_host: the same kernel on phases given as pairs, nseg (nnode + 1) + 1 rows (per
+        segment its nodes then its mid-point; the TZR row last)."""
+        ph = np.ascontiguousarray(ph_hi, dtype=np.float64).reshape(-1)
+        pl = np.ascontiguousarray(ph_lo, dtype=np.float64).reshape(-1)
+        dh = np.ascontiguousarray(dt_hi, dtype=np.float64).reshape(-1)
+        dl = np.ascontiguousarray(dt_lo, dtype=np.float64).reshape(-1)
+        if ph.size != nseg * (nnode + 1) + 1 or pl.size != ph.size or dh.size != nseg * nnode or dl.size != dh.size:
+            raise ValueError("the phases must hold nseg (nnode + 1) + 1 rows and dt nseg x nnode values")
+        out = self._polyco_fit_out(nseg, ncoeff) if 0 < nseg and 0 < ncoeff <= L.MAX_POLYCO_COEFF else [np.empty(1)] * 5
+        fh, fl = split_ld(f0)
+        self._check(self.L.pint_polyco_fit_host(self.ctx, nseg, nnode, ncoeff, L.ptr(ph), L.ptr(pl), L.ptr(dh), L.ptr(dl),
+                                                fh, fl, *[L.ptr(o) for o in out]))
+        return self._polyco_fit_result(out, nseg, ncoeff)
+
+    def set_polycos(self, hdr, c_hi=None, c_lo=None, ncoeff=None):
+        """pint_set_polycos: hdr (PC_NF, nent) field-major (tmid, t_start, t_stop pairs, rphase integer,
+        rphase fraction pair, f0 pair), the coefficients (nent, ncoeff) as pairs -- or None for both: the
+        coefficients and rphase of the last polyco_fit are adopted on the device (ncoeff then given)."""
+        hdr = np.ascontiguousarray(hdr, dtype=np.float64)
+        if hdr.ndim != 2 or hdr.shape[0] != L.PC_NF:
+            raise ValueError(f"hdr must be ({L.PC_NF}, nent), got {hdr.shape}")
+        nent = hdr.shape[1]
+        if c_hi is not None:
+            c_hi = np.ascontiguousarray(c_hi, dtype=np.float64)
+            c_lo = np.ascontiguousarray(c_lo, dtype=np.float64)
+            if c_hi.ndim != 2 or c_hi.shape[0] != nent or c_lo.shape != c_hi.shape:
+                raise ValueError(f"the coefficients must be two ({nent}, ncoeff) arrays")
+            ncoeff = c_hi.shape[1]
+        self._check(self.L.pint_set_polycos(self.ctx, nent, int(ncoeff or 0), L.ptr(hdr), L.ptr(c_hi), L.ptr(c_lo)))
+
+    def polyco_eval(self, t_hi, t_lo, want=1):
+        """pint_polyco_eval at the times (pairs) -> (int, frac, freq, fdot, n_uncovered); want: bit 0 the
+        phase, bit 1 the frequency, bit 2 its derivative (None for what was not asked for).  Uncovered
+        times hold NaN."""
+        th = np.ascontiguousarray(t_hi, dtype=np.float64).reshape(-1)
+        tl = np.ascontiguousarray(t_lo, dtype=np.float64).reshape(-1)
+        if tl.size != th.size:
+            raise ValueError("t_hi and t_lo differ in length")
+        outs = [np.empty(th.size) if want & b else None for b in (1, 1, 2, 4)]
+        cnt = C.c_int64(0)
+        self._check(self.L.pint_polyco_eval(self.ctx, th.size, L.ptr(th), L.ptr(tl), int(want), *[L.ptr(o) for o in outs],
+                                            C.byref(cnt)))
+        return (*outs, int(cnt.value))
+
+    def polyco_trig(self, t_hi, t_lo, weights=None, m=20):
+        """pint_polyco_trig -> ((2 m + 2,) C_1, S_1, ..., C_m, S_m, sum w, sum w^2, n_uncovered)."""
+        th = np.ascontiguousarray(t_hi, dtype=np.float64).reshape(-1)
+        tl = np.ascontiguousarray(t_lo, dtype=np.float64).reshape(-1)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if tl.size != th.size or (w is not None and w.size != th.size):
+            raise ValueError("t_hi, t_lo and the weights differ in length")
+        m = int(m)
+        out = np.empty(2 * max(m, 0) + 2)
+        cnt = C.c_int64(0)
+        self._check(self.L.pint_polyco_trig(self.ctx, th.size, L.ptr(th), L.ptr(tl), L.ptr(w), m, L.ptr(out), C.byref(cnt)))
+        return out, int(cnt.value)
+
     def debug_set_resids(self, resids):
         """Replace every instance's time residuals (list of n-arrays, seconds)."""
         flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float64) for r in resids]))

@@ -433,6 +433,59 @@ def load_tim(timfile, model=None, ephem=None, include_bipm=None, planets=None, i
     return t
 
 
+def get_TOAs_array(times, obs, errors=1.0, freqs=np.inf, flags=None, model=None, ephem=None, include_bipm=None,
+                   planets=False) -> TOAs:
+    """TOAs from an array of times at one observatory (toa.py:2729 get_TOAs_array), prepared on the host
+    like a tim file's (load_tim): ``times`` is a float64 or longdouble array of MJDs, or a tuple
+    (a, b) of arrays whose sum is the MJD (the integer and fractional parts, in either order) -- UTC at
+    observatories and the geocenter, TDB at the barycenter ("@").  errors (us) and freqs (MHz; 0 means
+    infinite frequency) are scalars or arrays; flags is a dict of values given to every TOA.  EPHEM,
+    CLOCK and PLANET_SHAPIRO come from ``model`` when the keywords leave them open; only the builtin
+    ephemeris is available offline and the TT(BIPM) table is not bundled, so ``include_bipm`` must end
+    up False (pass it, or a model with CLOCK TT(TAI)), as for load_tim."""
+    from . import prep
+    from .observatory import get_observatory_name
+    LD = np.longdouble
+    ephem = _ephem_choice(ephem, model)
+    _bipm_choice(include_bipm, model)
+    if planets is None:
+        planets = bool(model is not None and "PLANET_SHAPIRO" in model and model.PLANET_SHAPIRO.value)
+    a, b = times if isinstance(times, tuple) else (times, None)
+    s = np.atleast_1d(np.asarray(a)).astype(LD)
+    if b is not None:
+        s = s + np.atleast_1d(np.asarray(b)).astype(LD)
+    if s.ndim != 1 or s.size == 0:
+        raise ValueError("times must be a non-empty one-dimensional array (or a pair of them)")
+    day = np.floor(s)
+    frac = (s - day).astype(np.float64)
+    day = day.astype(np.float64)
+    n = s.size
+    site = get_observatory_name(obs)
+
+    def column(v, what):
+        v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        if v.size == 1:
+            v = np.repeat(v, n)
+        if v.shape != (n,):
+            raise AttributeError(f"Length of {what} array ({v.size}) must match length of times ({n})")
+        return v
+
+    sites = [site] * n
+    _warn_missing_clocks(sites, None)
+    cols = prep.prepare(day, frac, sites, None, planets=bool(planets))
+    fr = column(freqs, "frequency").copy()
+    fr[fr == 0.0] = np.inf
+    cols["freq_mhz"] = fr
+    cols["err_us"] = column(errors, "error")
+    cols["delta_pulse_number"] = np.zeros(n)
+    fc = {str(k): [str(v)] * n for k, v in (flags or {}).items()}
+    t = TOAs(cols, fc, None, "", sites)
+    t.ephem = ephem
+    t.clock = "TT(TAI)"
+    t.prepared = {"ephem": ephem, "include_bipm": False, "clock_files": None, "planets": bool(planets)}
+    return t
+
+
 def tzr_row(model, prepared) -> dict:
     """get_TZR_toa (absolute_phase.py:79-127) prepared like the TOAs: TZRMJD (its parsed
     day + fraction) at TZRSITE (default barycenter) with TZRFRQ (none/0 -> infinite)."""
