@@ -6917,9 +6917,6 @@ struct pint_ctx {
     int degv_cap = 0;
     InstConst* d_ic = nullptr;  // per-instance constants (k_prep)
     InstConst* d_ic0 = nullptr; // the constants of the table snapshot (pint_save_tables)
-    bool apply_req = false;     // pint_fit_step_apply: fuse the apply into the solve if possible
-    bool apply_done = false;    //   ... and it was fused
-    double apply_lam = 1.0;
     bool ic0_valid = false;
     double *d_dmxv = nullptr, *d_Sd = nullptr, *d_DD = nullptr, *d_DCS = nullptr;  // sparse-DMX layout
     double* d_dfac = nullptr;  // PLDMNoise basis scale per TOA row (only with PLDMNoise pulsars)
@@ -9340,162 +9337,201 @@ int pint_read_designmatrix(pint_ctx* ctx, double* M) {
     return PINT_OK;
 }
 
-// Gram + solve for every instance; requires pint_eval(want_M=1) on the current state.
-int pint_fit_step(pint_ctx* ctx, int mode) {
-    if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
-    if (flush_restore(ctx)) return PINT_E_HIP;
-    hipSetDevice(ctx->device);
-    // deferred reads of this slot's outputs enqueued since the last step_end go first (this
-    // solve rewrites them)
-    if (int rc = flush_cq_now(ctx)) return rc;
-    if (ctx->r2_pending && !can_defer_r2(ctx)) flush_r2(ctx);  // (a kernel below reads d_rt)
-    const GvResid gvr{ctx->d_rp, ctx->d_ftay, ctx->d_rpart, ctx->r2_pending ? 1 : 0, ctx->efz ? ctx->d_epart : nullptr};
+// ---------------------------------------------------------------------------------
+// The fit step's host side: the batch's widths (fit_shape), the launch plan decided from
+// them (plan_fit_step: host arithmetic only, and every refusal), then one launch stage per
+// kernel family that does what the plan says.  A new kernel variant is a field of FitPlan,
+// chosen in plan_fit_step and read by its stage; a template family has one table or one
+// pointer choice, and one call site.
+// ---------------------------------------------------------------------------------
+}  // extern "C" (the kernel tables are templates)
+// k_gram<T, gram_ch(T), VIRT>: [the ECORR variant][T - 1], T = 1..GMAXT_ALL upper tiles per wave
+using GramKernel = decltype(&k_gram<1, gram_ch(1), false>);
+template <bool VIRT, size_t... T>
+constexpr std::array<GramKernel, sizeof...(T)> gram_kernel_row(std::index_sequence<T...>) {
+    return {{k_gram<(int)T + 1, gram_ch((int)T + 1), VIRT>...}};
+}
+constexpr std::array<GramKernel, GMAXT_ALL> GRAM_KERNELS[2] = {
+    gram_kernel_row<false>(std::make_index_sequence<GMAXT_ALL>{}), gram_kernel_row<true>(std::make_index_sequence<GMAXT_ALL>{})};
+// k_gram_v<R, C, VB> by launch key 10 (R - 1) + C: R row tiles (1..3) x C column tiles (R..7), [VB]
+using GramVKernel = decltype(&k_gram_v<1, 1, false>);
+struct GramVEntry {
+    int key;
+    GramVKernel kern[2];
+};
+template <int R, int C>
+constexpr GramVEntry gram_v_entry() {
+    return {10 * (R - 1) + C, {k_gram_v<R, C, false>, k_gram_v<R, C, true>}};
+}
+constexpr GramVEntry GRAM_V_KERNELS[PINT_PLAN_MAXVKEY] = {
+    gram_v_entry<1, 1>(), gram_v_entry<1, 2>(), gram_v_entry<1, 3>(), gram_v_entry<1, 4>(), gram_v_entry<1, 5>(),
+    gram_v_entry<1, 6>(), gram_v_entry<1, 7>(), gram_v_entry<2, 2>(), gram_v_entry<2, 3>(), gram_v_entry<2, 4>(),
+    gram_v_entry<2, 5>(), gram_v_entry<2, 6>(), gram_v_entry<2, 7>(), gram_v_entry<3, 3>(), gram_v_entry<3, 4>(),
+    gram_v_entry<3, 5>(), gram_v_entry<3, 6>(), gram_v_entry<3, 7>()};
+extern "C" {
+
+constexpr size_t FIT_LDS = 160 * 1024;  // a workgroup's LDS
+static inline int nb16(int k) { return (k + 15) / 16; }
+
+// The maxima and flags of the batch's pulsars that the step's decisions read (one pass).
+struct FitShape {
+    int Kn;           // widest noise block, 2 nred + 1 (mode 1)
+    int Ks_rest;      // widest system of the general solve: the pulsars off the compact DMX layout
+    int Ks_all;       //   ... every pulsar
+    int ndmx;         // pulsars on the compact DMX layout (k_solve_dmx's)
+    bool dmx_fit;     //   ... each within k_solve_dmx's block counts
+    int nbd, nbk;     //   ... their most dense / DMX 16-column blocks
+    size_t lds_x;     //   ... the solve data of the widest, bytes
+    int maxKd;        //   ... widest dense part (k_dmx_rows)
+    bool any_gather;  //   ... a bin's rows are not contiguous (k_dmx)
+    bool noise;       // mode 1: a pulsar has red noise or ECORR (a Woodbury Sigma)
+    int nbs_sig;      //   ... the widest Sigma's 16-column blocks
+    bool ones;        //   ... with a frozen PHOFF: the Woodbury ones row
+    int maxKp;        // widest padded Gram (k_greduce)
+    bool all_vg;      // every pulsar on the generated-Fourier path (the fused apply)
+    int maxts;        // longest table (the fused apply's staging)
+};
+
+static FitShape fit_shape(const pint_ctx* ctx, int mode) {
+    FitShape s{};
+    s.dmx_fit = s.all_vg = true;
+    s.maxKp = 16;
+    int kn_sig = 0;
+    for (int pi : ctx->upsr) {
+        const PsrHost& ph = ctx->psrs[pi];
+        const pint_spec_t& sp = ph.spec;
+        const PsrDev& pd = ph.dev;
+        const bool ds = ctx->m_compact && pd.dsplit;
+        const bool noisy = mode == 1 && (sp.nred > 0 || pd.nep > 0);
+        const int kn = mode == 1 ? 2 * sp.nred + 1 : 0, ks = mode == 0 ? sp.ncol : ph.K;
+        s.Kn = std::max(s.Kn, kn);
+        s.Ks_all = std::max(s.Ks_all, ks);
+        if (noisy) s.noise = true, kn_sig = std::max(kn_sig, kn);
+        if (noisy && sp.o_PHOFF >= 0 && !sp.wb_noones) s.ones = true;
+        s.maxKp = std::max(s.maxKp, ds ? pd.Kpd : pd.Kp);
+        s.all_vg = s.all_vg && ds && pd.vg;
+        s.maxts = std::max(s.maxts, sp.tstride);
+        if (!ds) {
+            s.Ks_rest = std::max(s.Ks_rest, ks);
+            continue;
+        }
+        s.ndmx++;
+        const int nbd = nb16(mode == 0 ? pd.red0c : pd.Kd), nbk = nb16(pd.ndc), nbs = nb16(kn);
+        const int blk = nbd * (nbd + 1) / 2 + nbd * nbk;
+        if (blk > SD_MAXBLK || nbd > 17 || nbs > BS_MAXNB) s.dmx_fit = false;
+        s.lds_x = std::max(s.lds_x, sizeof(double) * ((size_t)std::max(blk, nbs * (nbs + 1) / 2) * 256 +
+                                                      (size_t)(5 * nbd + 6 * nbk) * 16));
+        s.nbd = std::max(s.nbd, nbd);
+        s.nbk = std::max(s.nbk, nbk);
+        s.maxKd = std::max(s.maxKd, pd.Kd);
+        if (!pd.dcontig) s.any_gather = true;
+    }
+    s.nbs_sig = nb16(kn_sig);
+    return s;
+}
+
+// What one pint_fit_step launches.  err set: the batch is refused, nothing is launched and
+// pub is all-zero.
+struct FitPlan {
+    const char* err;
+    pint_plan_t pub;  // as pint_last_plan reports it; the stages read their kernel choices from it
+    int mode, nparts, skip;
+    bool ecorr;       // mode 1 with ECORR epochs: k_ecorr, the ECORR Gram variants, k_ecorr_dmx
+    bool ones, vgp;
+    bool ext_t, gram_mark;  // the Gram's timing events: on k_gram_v's dispatch packets, or marker packets
+    size_t lds_rows;        // k_dmx_rows
+    struct GramGroup {      // per k_gram launch group (kern null: k_gram_s; kern_ecorr null: none)
+        GramKernel kern, kern_ecorr;
+        size_t lds;
+    } gram[GMAXT_ALL + 1];
+    struct GramVGroup {     // per k_gram_v launch group
+        GramVKernel kern;
+        uint32_t lds;
+    } gramv[PINT_PLAN_MAXVKEY];
+    int nbg;                // k_greduce's blocks over the widest Gram
+    size_t lds_s, lds_x, lds_dyn, lds_col;  // k_sigma, k_cov_dmx, k_solve_dmx, k_solve
+    bool xw, pre, w8, apply_tail;           // k_solve_dmx: exports for k_cov_dmx, after k_schur, 8 waves, fused apply
+    int mnb;                // k_schur's blocks per instance
+    size_t lds_schur;
+    int ldsw, ldsw1;        // k_solve_blk: doubles per instance (ldsw1: + the one-wave form's scratch vectors)
+};
+
+static const GramVEntry* gram_v_kernels(int key) {
+    for (const GramVEntry& e : GRAM_V_KERNELS)
+        if (e.key == key) return &e;
+    return nullptr;
+}
+
+static FitPlan plan_refused(const char* why) {
+    FitPlan p{};
+    p.err = why;
+    return p;
+}
+
+// The plan of pint_fit_step(mode) on the context's batch: the DMX-eliminated solve
+// (k_solve_dmx) for compact-layout instances when every such instance fits its LDS budget;
+// the others (and everything in the full layout) go to the blocked MFMA solve, or the
+// column-by-column one beyond its budget.  Host arithmetic on the batch's widths only, so a
+// batch no kernel can take is refused with nothing enqueued and no state changed.
+// apply_req: pint_fit_step_apply asks for the apply in the solve; sampled: this call's Gram
+// carries timing events (PINT_OPT_TIMING_EVERY).
+static FitPlan plan_fit_step(const pint_ctx* ctx, int mode, bool apply_req, bool sampled) {
+    const bool cmp = ctx->m_compact;
     if (ctx->wbfit) {
         // k_wb_gram adds the DM rows to the compact normal equations only: a design matrix in
         // the full layout, or a wideband pulsar that stays on it (fewer than 8 free DMX bins, a
         // TOA in two free bins, ECORR epochs across bins), is refused instead of taking a
         // TOA-only step
-        if (!ctx->m_compact) {
-            ctx->err = "wideband fit: the DM rows need the compact fit layout (pint_eval with want_M = 2)";
-            return PINT_E_INVALID;
-        }
+        if (!cmp) return plan_refused("wideband fit: the DM rows need the compact fit layout (pint_eval with want_M = 2)");
         // k_wb_gram carries at most WB_MAXC free DM-type columns (DM Taylor terms + DMJUMPs):
         // refuse more instead of leaving the extra columns without their DM rows
         for (int pi : ctx->upsr) {
             const pint_spec_t& sp = ctx->psrs[pi].spec;
             if (!ctx->psrs[pi].dev.wb) continue;
-            if (!ctx->psrs[pi].dev.dsplit) {
-                ctx->err = "wideband fit: a pulsar with wideband DM data is not on the compact DMX layout "
-                           "(>= 8 free DMX bins, no TOA in two free bins, every ECORR epoch within one bin)";
-                return PINT_E_INVALID;
-            }
+            if (!ctx->psrs[pi].dev.dsplit)
+                return plan_refused("wideband fit: a pulsar with wideband DM data is not on the compact DMX layout "
+                                    "(>= 8 free DMX bins, no TOA in two free bins, every ECORR epoch within one bin)");
             int m = 0;
             for (int c = 0; c < sp.ncol; c++)
                 m += (sp.col_kind[c] == PINT_COL_DM || sp.col_kind[c] == PINT_COL_ZERO || sp.col_kind[c] == PINT_COL_NESW);
-            if (m > WB_MAXC) {
-                ctx->err = "wideband fit: more than 8 free DM-type columns (DM Taylor terms + DMJUMPs + NE_SW)";
-                return PINT_E_INVALID;
-            }
+            if (m > WB_MAXC)
+                return plan_refused("wideband fit: more than 8 free DM-type columns (DM Taylor terms + DMJUMPs + NE_SW)");
         }
     }
-    const int nparts = ctx->nsplit + ((mode == 1 && ctx->max_nep > 0) ? 1 : 0);
-    const int cmp = ctx->m_compact;
-    // solve plan: the DMX-eliminated solve (k_solve_dmx) for compact-layout instances when
-    // every such instance fits its LDS budget; the others (and everything in the full
-    // layout) go to the blocked MFMA solve, or the column-by-column one beyond its budget.
-    // Host arithmetic on the batch's widths only, done before the first launch so that a
-    // batch no solve kernel can take is refused with nothing enqueued.
-    int Ks = 0, Kn = 0, ndmx_inst = 0;
-    bool dmx_ok = cmp && ctx->blocked_solve;
-    size_t lds_x = 0;
-    for (int pi : ctx->upsr) {
-        const PsrHost& ph = ctx->psrs[pi];
-        const pint_spec_t& sp = ph.spec;
-        const int kn = mode == 1 ? 2 * sp.nred + 1 : 0;
-        Kn = std::max(Kn, kn);
-        if (cmp && ph.dev.dsplit) {
-            ndmx_inst++;
-            const int kd = mode == 0 ? ph.dev.red0c : ph.dev.Kd;
-            const int nbd = (kd + 15) / 16, nbk = (ph.dev.ndc + 15) / 16, nbs = (kn + 15) / 16;
-            const int blk = nbd * (nbd + 1) / 2 + nbd * nbk;
-            if (blk > SD_MAXBLK || nbd > 17 || nbs > BS_MAXNB) dmx_ok = false;
-            lds_x = std::max(lds_x, sizeof(double) * ((size_t)std::max(blk, nbs * (nbs + 1) / 2) * 256 +
-                                                      (size_t)(5 * nbd + 6 * nbk) * 16));
-            if (lds_x > 160 * 1024 - 512) dmx_ok = false;  // (the kernel's static LDS beside it)
-        } else {
-            Ks = std::max(Ks, mode == 0 ? sp.ncol : ph.K);
-        }
-    }
-    if (!dmx_ok) {  // every instance through the general solve
-        for (int pi : ctx->upsr) Ks = std::max(Ks, mode == 0 ? ctx->psrs[pi].spec.ncol : ctx->psrs[pi].K);
-        ndmx_inst = 0;
-    }
-    const int skip = ndmx_inst > 0 ? 1 : 0;
-    // Woodbury Sigma factor: in k_solve_dmx's grid when every instance is solved there, else
-    // on the side stream, concurrent with the per-instance solve
-    int do_sigma = 0, fuse_sigma = 0, side_sigma = 0, nbs_sig = 0;
-    size_t lds_s = 0;
-    if (mode == 1) {
-        int kn = 0;
-        bool any = false;
-        for (int pi : ctx->upsr) {
-            const PsrHost& ph = ctx->psrs[pi];
-            if (ph.spec.nred > 0 || ph.dev.nep > 0) { any = true; kn = std::max(kn, 2 * ph.spec.nred + 1); }
-        }
-        nbs_sig = (kn + 15) / 16;
-        lds_s = sizeof(double) * (size_t)nbs_sig * (nbs_sig + 1) / 2 * 256;
-        if (any && nbs_sig <= BS_MAXNB && ctx->blocked_solve && skip && Ks == 0) fuse_sigma = 1;
-        else if (any && nbs_sig <= BS_MAXNB && ctx->blocked_solve) side_sigma = 1;
-        else if (any) do_sigma = 1;  // the column-by-column solve factors it (beyond the blocked LDS budget)
-    }
-    const int nbx = std::max((Ks + 15) / 16, (Kn + 15) / 16);
-    const bool col_solve = !(skip && Ks == 0) && !(nbx <= BS_MAXNB && ctx->blocked_solve);
-    const size_t lds_col = sizeof(double) * ((size_t)ctx->maxK * (ctx->maxK + 1) / 2 + 5 * ctx->maxK + 8);
-    ctx->plan = pint_plan_t{};
-    if (col_solve && lds_col > 160 * 1024) { ctx->err = "normal matrix too large for LDS solve"; return PINT_E_INVALID; }
-    if (do_sigma && !col_solve) {  // Sigma too large for k_sigma but the main solve on the blocked kernels
-        ctx->err = "Woodbury Sigma too large for the LDS factorisation";
-        return PINT_E_INVALID;
-    }
-    pint_plan_t pl{};
+    const FitShape s = fit_shape(ctx, mode);
+    FitPlan p{};
+    pint_plan_t& pl = p.pub;
+    p.mode = mode;
+    p.ecorr = mode == 1 && ctx->max_nep > 0;
+    p.nparts = ctx->nsplit + (p.ecorr ? 1 : 0);
+    p.ones = s.ones;
     pl.nsplit = ctx->nsplit;
-    pl.fuse_sigma = fuse_sigma;
-    pl.side_sigma = side_sigma;
-    pl.do_sigma = do_sigma;
-    if (ctx->sigma_pending) {  // the previous k_sigma reads the Gram buffer this step overwrites
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));
-        ctx->sigma_pending = false;
-    }
-    record(ctx, 6);
-    if (mode == 1 && ctx->max_nep > 0) {
-        if (any_copy_pend(ctx)) {  // the copy stream's noise realisations read esum / eD
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied, 0));
-            clear_copy_pend(ctx);
-        }
-        hipLaunchKernelGGL(k_ecorr, dim3((ctx->max_nep + 3) / 4, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, ctx->d_M, ctx->d_rt, ctx->d_esum, ctx->d_eD, ctx->d_eW, ctx->m_compact,
-                           ctx->d_dmxv, ctx->d_eC);
-        HIPCHK(hipGetLastError());
-    }
-    const bool vgp = cmp && ctx->n_vg > 0;  // k_gram_v path for the vg instances
-    // PhaseOffset with a frozen PHOFF and correlated noise: the Woodbury ones row (k_onesrow)
-    const double* ones = nullptr;
-    if (mode == 1) {
-        for (int pi : ctx->upsr) {
-            const PsrHost& ph = ctx->psrs[pi];
-            if (ph.spec.o_PHOFF >= 0 && !ph.spec.wb_noones && (ph.spec.nred > 0 || ph.dev.nep > 0)) ones = ctx->d_ones;
-        }
-        if (ones) {
-            hipLaunchKernelGGL(k_onesrow, dim3(ctx->ninst), dim3(64), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_esum, ctx->d_eD, ctx->d_eW, ctx->d_eC, cmp, ctx->d_M, ctx->d_ones);
-            HIPCHK(hipGetLastError());
-        }
-    }
+    // the solves.  lds_x beside k_solve_dmx's static LDS
+    const bool dmx_ok = cmp && ctx->blocked_solve && s.dmx_fit && s.lds_x <= FIT_LDS - 512;
+    p.skip = dmx_ok && s.ndmx > 0;
+    const int Ks = p.skip ? s.Ks_rest : s.Ks_all;  // (else every instance through the general solve)
+    const bool all_dmx = p.skip && Ks == 0;
+    const int nbx = std::max(nb16(Ks), nb16(s.Kn));
+    const bool col_solve = !all_dmx && !(nbx <= BS_MAXNB && ctx->blocked_solve);
+    p.lds_x = s.lds_x;
+    p.lds_col = sizeof(double) * ((size_t)ctx->maxK * (ctx->maxK + 1) / 2 + 5 * ctx->maxK + 8);
+    if (col_solve && p.lds_col > FIT_LDS) return plan_refused("normal matrix too large for LDS solve");
+    // Woodbury Sigma factor: in k_solve_dmx's grid when every instance is solved there, else
+    // on the side stream, concurrent with the per-instance solve; beyond the blocked LDS
+    // budget the column-by-column solve factors it
+    const bool blk_sigma = s.noise && s.nbs_sig <= BS_MAXNB && ctx->blocked_solve;
+    pl.fuse_sigma = blk_sigma && all_dmx;
+    pl.side_sigma = blk_sigma && !all_dmx;
+    pl.do_sigma = s.noise && !blk_sigma;
+    pl.sigma_waves = pl.side_sigma ? (s.nbs_sig <= 5 ? 4 : 16) : 0;
+    p.lds_s = sizeof(double) * (size_t)s.nbs_sig * (s.nbs_sig + 1) / 2 * 256;
+    if (pl.do_sigma && !col_solve)  // Sigma too large for k_sigma but the main solve on the blocked kernels
+        return plan_refused("Woodbury Sigma too large for the LDS factorisation");
     if (cmp && ctx->max_ndc > 0 && ctx->any_dmx_rows) {
-        int maxKd = 0;
-        bool any_gather = false;
-        for (int pi : ctx->upsr) {
-            const PsrDev& pd = ctx->psrs[pi].dev;
-            if (pd.dsplit) maxKd = std::max(maxKd, pd.Kd);
-            if (pd.dsplit && !pd.dcontig) any_gather = true;
-        }
-        size_t lds = sizeof(double) * (DMX_RS * ((maxKd + 2) | 1) + 2 * DMX_RS);
-        hipLaunchKernelGGL(k_dmx_rows, dim3(ctx->max_ndc, ctx->ninst), dim3(256), lds, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, ctx->d_M, ctx->d_rt, ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
-        HIPCHK(hipGetLastError());
         pl.dmx_rows = 1;
-        pl.dmx = any_gather ? 1 : 0;
-        pl.ecorr_dmx = (mode == 1 && ctx->max_nep > 0) ? 1 : 0;
-        if (any_gather) {
-            hipLaunchKernelGGL(k_dmx, dim3(ctx->max_ndc, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs,
-                               ctx->d_inst, ctx->d_M, ctx->d_rt, ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
-            HIPCHK(hipGetLastError());
-        }
-        if (mode == 1 && ctx->max_nep > 0) {  // the ECORR elimination's share of the DMX rows
-            hipLaunchKernelGGL(k_ecorr_dmx, dim3(ctx->max_ndc, ctx->ninst), dim3(64), 0, ctx->stream, ctx->d_psrs,
-                               ctx->d_inst, ctx->d_esum, ctx->d_eD, ctx->d_eC, ctx->d_Sd, ctx->d_DD);
-            HIPCHK(hipGetLastError());
-        }
+        pl.dmx = s.any_gather;
+        pl.ecorr_dmx = p.ecorr;  // the ECORR elimination's share of the DMX rows
+        p.lds_rows = sizeof(double) * (DMX_RS * ((s.maxKd + 2) | 1) + 2 * DMX_RS);
     }
     // Gram-kernel timing: when the whole Gram is k_gram_v launches, the slot's start/stop
     // events ride on the first/last dispatch packet (hipExtLaunchKernel) instead of marker
@@ -9503,298 +9539,318 @@ int pint_fit_step(pint_ctx* ctx, int mode) {
     // PINT_OPT_TIMING_EVERY k: the Gram events ride on every k-th fit step only (each event
     // pair still costs the stream a few us; the average over the sampled launches is the
     // kernel's time)
-    const bool sampled = ctx->timing_every <= 1 || (ctx->gram_calls++ % ctx->timing_every) == 0;
+    const std::vector<KpGroup>& groups = cmp ? ctx->kp_groups_c : ctx->kp_groups;
+    p.vgp = cmp && ctx->n_vg > 0;  // k_gram_v path for the vg instances
     const bool gram_t = !ctx->no_events && !ctx->capturing && ((ctx->timing_mask >> 6) & 1) && sampled;
-    const bool ext_t = gram_t && vgp && (cmp ? ctx->kp_groups_c : ctx->kp_groups).empty() &&
-                       !ctx->kp_groups_v.empty();
-    const bool gram_mark = sampled && !ext_t;  // marker-packet events (the other Gram paths)
-    if (gram_mark) record(ctx, 12);
-    {
-        // instances are launched in groups of equal tiles-per-wave T (template parameter);
-        // per-instance tile counts are recomputed in-kernel from their own Kp.
-        const std::vector<KpGroup>& groups = cmp ? ctx->kp_groups_c : ctx->kp_groups;
-        for (int g = 0; g < (int)groups.size(); g++) {
-            const KpGroup& kg = groups[g];
-            const int T = kg.T;
-            const InstDev* di = (cmp ? ctx->d_inst_sorted_c : ctx->d_inst_sorted) + kg.first;
-            if (T == 0) {  // small instances: k_gram_s (the ECORR rows, if any, by k_gram<1> below)
-                hipLaunchKernelGGL(k_gram_s, dim3(ctx->nsplit, (kg.count + 3) / 4), dim3(256), 0, ctx->stream,
-                                   ctx->d_psrs, di, kg.count, ctx->d_M, ctx->d_rt, ctx->nsplit, cmp, ctx->d_G,
-                                   ctx->d_colsq);
-                pl.gram_s = 1;
-                if (mode == 1 && ctx->max_nep > 0) pl.gram_ecorr = 1, pl.gram_t_mask |= 1 << 1;
-                if (mode == 1 && ctx->max_nep > 0)
-                    hipLaunchKernelGGL((k_gram<1, gram_ch(1), true>), dim3(1, kg.count), dim3(GTHREADS),
-                                       sizeof(double) * ((size_t)kg.maxKp * (gram_ch(1) + 2) + gram_ch(1)),
-                                       ctx->stream, ctx->d_psrs, di, ctx->d_M, ctx->d_rt, ctx->d_esum, ctx->d_eD,
-                                       ctx->nsplit, cmp, ctx->d_G, ctx->d_colsq);
-                continue;
-            }
-            const int CH = gram_ch(T);
-            size_t lds = sizeof(double) * ((size_t)kg.maxKp * (CH + 2) + CH);
-            for (int virt = 0; virt < 2; virt++) {
-                if (virt && !(mode == 1 && ctx->max_nep > 0)) break;
-                dim3 grid(virt ? 1 : ctx->nsplit, kg.count);
-                if (T >= 1 && T <= GMAXT_ALL) pl.gram_t_mask |= 1 << T, pl.gram_ecorr |= virt;
-#define PINT_GRAM_CASE(TT)                                                                                        \
-                case TT:                                                                                           \
-                    if (virt) hipLaunchKernelGGL((k_gram<TT, gram_ch(TT), true>), grid, dim3(GTHREADS), lds,      \
-                                                 ctx->stream, ctx->d_psrs, di, ctx->d_M, ctx->d_rt, ctx->d_esum,  \
-                                                 ctx->d_eD, ctx->nsplit, cmp, ctx->d_G, ctx->d_colsq);            \
-                    else hipLaunchKernelGGL((k_gram<TT, gram_ch(TT), false>), grid, dim3(GTHREADS), lds,         \
-                                            ctx->stream, ctx->d_psrs, di, ctx->d_M, ctx->d_rt, ctx->d_esum,       \
-                                            ctx->d_eD, ctx->nsplit, cmp, ctx->d_G, ctx->d_colsq);                 \
-                    break;
-                switch (T) {
-                    PINT_GRAM_CASE(1) PINT_GRAM_CASE(2) PINT_GRAM_CASE(3) PINT_GRAM_CASE(4) PINT_GRAM_CASE(5)
-                    PINT_GRAM_CASE(6) PINT_GRAM_CASE(7) PINT_GRAM_CASE(8) PINT_GRAM_CASE(9)
-                    default: ctx->err = "Kp out of range"; return PINT_E_INVALID;
-                }
-#undef PINT_GRAM_CASE
-            }
-        }
+    p.ext_t = gram_t && p.vgp && groups.empty() && !ctx->kp_groups_v.empty();
+    p.gram_mark = sampled && !p.ext_t;
+    // instances are launched in groups of equal tiles-per-wave T (template parameter);
+    // per-instance tile counts are recomputed in-kernel from their own Kp.  T = 0, small
+    // instances: k_gram_s (the ECORR rows, if any, by k_gram<1>)
+    for (size_t g = 0; g < groups.size(); g++) {
+        const int T = groups[g].T, Te = std::max(T, 1);
+        if ((int)g > GMAXT_ALL || T < 0 || T > GMAXT_ALL) return plan_refused("Kp out of range");
+        const int CH = gram_ch(Te);
+        p.gram[g] = {T ? GRAM_KERNELS[0][T - 1] : nullptr, p.ecorr ? GRAM_KERNELS[1][Te - 1] : nullptr,
+                     sizeof(double) * ((size_t)groups[g].maxKp * (CH + 2) + CH)};
+        if (T) pl.gram_t_mask |= 1 << T;
+        else pl.gram_s = 1;
+        if (p.ecorr) pl.gram_ecorr = 1, pl.gram_t_mask |= 1 << Te;
     }
-    if (ext_t)  // (the timing events are created at first use)
-        for (int i : {12, 13})
-            if (!ctx->ev[i]) HIPCHK(hipEventCreate(&ctx->ev[i]));
-    if (vgp) {
-        for (size_t gi = 0; gi < ctx->kp_groups_v.size(); gi++) {
-            const KpGroup& kg = ctx->kp_groups_v[gi];
-            const InstDev* di = ctx->d_inst_sorted_v + kg.first;
-            hipEvent_t e0 = (ext_t && gi == 0) ? ctx->ev[12] : nullptr;
-            hipEvent_t e1 = (ext_t && gi + 1 == ctx->kp_groups_v.size()) ? ctx->ev[13] : nullptr;
-            dim3 grid(ctx->nsplit, kg.count);
-            const size_t lds = sizeof(double) * std::max<size_t>((size_t)GVB * (kg.maxKp + (ctx->vb_on && kg.maxKp <= 96 ? 33 : 17)) * (VCH + 2),
-                                                                 std::max(GW * VTG * 256, GW * 256 + 256));
-#define PINT_GRAMV(R_, C_)                                                                                       \
-            if (ctx->vb_on && C_ <= 6)                                                                               \
-                hipExtLaunchKernelGGL((k_gram_v<R_, C_, true>), grid, dim3(GW * 64), (uint32_t)lds, ctx->stream, e0, e1, \
-                                      0u, (const PsrDev*)ctx->d_psrs, di, (const double*)ctx->d_M,                    \
-                                      (const double*)ctx->d_rt, (const double*)ctx->d_dmxv, ctx->nsplit, ctx->d_G,     \
-                                      ctx->d_Sdp, ctx->d_colsq, ctx->d_TSp, ctx->d_BFp, ctx->gvdbg, gvr);              \
-            else                                                                                                     \
-                hipExtLaunchKernelGGL((k_gram_v<R_, C_, false>), grid, dim3(GW * 64), (uint32_t)lds, ctx->stream, e0, e1, \
-                                      0u, (const PsrDev*)ctx->d_psrs, di, (const double*)ctx->d_M,                    \
-                                      (const double*)ctx->d_rt, (const double*)ctx->d_dmxv, ctx->nsplit, ctx->d_G,     \
-                                      ctx->d_Sdp, ctx->d_colsq, ctx->d_TSp, ctx->d_BFp, ctx->gvdbg, gvr)
-            switch (kg.T) {
-                case 1: PINT_GRAMV(1, 1); break;
-                case 2: PINT_GRAMV(1, 2); break;
-                case 3: PINT_GRAMV(1, 3); break;
-                case 4: PINT_GRAMV(1, 4); break;
-                case 5: PINT_GRAMV(1, 5); break;
-                case 6: PINT_GRAMV(1, 6); break;
-                case 7: PINT_GRAMV(1, 7); break;
-                case 12: PINT_GRAMV(2, 2); break;
-                case 13: PINT_GRAMV(2, 3); break;
-                case 14: PINT_GRAMV(2, 4); break;
-                case 15: PINT_GRAMV(2, 5); break;
-                case 16: PINT_GRAMV(2, 6); break;
-                case 17: PINT_GRAMV(2, 7); break;
-                case 23: PINT_GRAMV(3, 3); break;
-                case 24: PINT_GRAMV(3, 4); break;
-                case 25: PINT_GRAMV(3, 5); break;
-                case 26: PINT_GRAMV(3, 6); break;
-                case 27: PINT_GRAMV(3, 7); break;
-                default: ctx->err = "k_gram_v layout out of range"; return PINT_E_INVALID;
-            }
-#undef PINT_GRAMV
-            if (pl.nvkey < PINT_PLAN_MAXVKEY) {
-                pl.vkey[pl.nvkey] = kg.T;
-                pl.vkey_vb[pl.nvkey++] = (ctx->vb_on && kg.T % 10 <= 6) ? 1 : 0;
-            }
-        }
-        if (ext_t) ctx->rec[12] = ctx->rec[13] = true;
-        else if (gram_mark) record(ctx, 13);
-    } else if (gram_mark) {
-        record(ctx, 13);
+    for (size_t g = 0; p.vgp && g < ctx->kp_groups_v.size(); g++) {
+        const KpGroup& kg = ctx->kp_groups_v[g];
+        const GramVEntry* e = gram_v_kernels(kg.T);
+        if (g >= PINT_PLAN_MAXVKEY || !e) return plan_refused("k_gram_v layout out of range");
+        const int vb = (ctx->vb_on && kg.T % 10 <= 6) ? 1 : 0;
+        const size_t lds = sizeof(double) * std::max<size_t>((size_t)GVB * (kg.maxKp + (ctx->vb_on && kg.maxKp <= 96 ? 33 : 17)) * (VCH + 2),
+                                                             std::max(GW * VTG * 256, GW * 256 + 256));
+        p.gramv[g] = {e->kern[vb], (uint32_t)lds};
+        pl.vkey[pl.nvkey] = kg.T;
+        pl.vkey_vb[pl.nvkey++] = vb;
     }
-    HIPCHK(hipGetLastError());
-    GredArgs gra{ctx->nsplit, nparts, cmp, ctx->vb_on, ctx->d_G, ctx->d_colsq, ctx->d_Sdp, ctx->d_dmxv,
-                 ctx->d_Sd, ctx->d_DD, ctx->d_DCS, ctx->d_BFp};
-    if (nparts > 1 || vgp) {
-        int maxKp = 16;
-        for (int pi : ctx->upsr) {
-            const PsrDev& pd = ctx->psrs[pi].dev;
-            maxKp = std::max(maxKp, (cmp && pd.dsplit) ? pd.Kpd : pd.Kp);
-        }
-        // (round 4: the column sums of squares on threads of their own, beside the Gram's
-        // chains, measured no faster -- 11.3-11.9 vs 10.5-10.9 us at 9 pulsars)
-        const int nbg = (maxKp * maxKp + 255) / 256;
-        record(ctx, 14);
-        hipLaunchKernelGGL(k_greduce, dim3(nbg + (vgp ? (ctx->max_ndc + 3) / 4 : 0), ctx->ninst), dim3(256), 0, ctx->stream,
-                           ctx->d_psrs, ctx->d_inst, nbg, gra);
-        HIPCHK(hipGetLastError());
-        pl.greduce = 1;
-        record(ctx, 15);
-    }
-    if (ctx->wbfit && cmp) {  // WidebandTOAFitter: the DM rows join the normal equations
-        if (int rc = ensure_ic_solar_wind(ctx)) return rc;
-        hipLaunchKernelGGL(k_wb_gram, dim3(ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                           ctx->d_tables, ctx->d_ic, ctx->nsplit, ctx->d_G, ctx->d_colsq, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
-        HIPCHK(hipGetLastError());
-        pl.wb_gram = 1;
-    }
-    record(ctx, 7);
-    if (side_sigma) {
-        HIPCHK(hipEventRecord(ctx->ev_gram, ctx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->sstream, ctx->ev_gram, 0));
-        pl.sigma_waves = nbs_sig <= 5 ? 4 : 16;
-        if (nbs_sig <= 5)
-            hipLaunchKernelGGL(k_sigma<4>, dim3(ctx->ninst), dim3(256), lds_s, ctx->sstream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_tables, ctx->d_G, cmp, ctx->d_Sd, ctx->d_DD, ctx->d_sigL, ctx->d_status, ones);
-        else
-            hipLaunchKernelGGL(k_sigma<16>, dim3(ctx->ninst), dim3(1024), lds_s, ctx->sstream, ctx->d_psrs,
-                               ctx->d_inst, ctx->d_tables, ctx->d_G, cmp, ctx->d_Sd, ctx->d_DD, ctx->d_sigL,
-                               ctx->d_status, ones);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ctx->ev_sigma, ctx->sstream));
-        ctx->sigma_pending = true;
-    }
-    if (ctx->copy_pend[ctx->slot]) {  // this slot's outputs may still be in flight to the host
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied, 0));  // (the latest copies: covers them)
-        clear_copy_pend(ctx);
-    }
-    ctx->cov_pending = false;
-    if (skip) {
+    pl.greduce = p.nparts > 1 || p.vgp;
+    p.nbg = (s.maxKp * s.maxKp + 255) / 256;
+    pl.wb_gram = ctx->wbfit && cmp;  // WidebandTOAFitter: the DM rows join the normal equations
+    if (p.skip) {
         // deferred covariance for batches (a single fit would pay a launch on its read instead)
         // (and in lazy, pipelined steps of any size: the read runs k_cov_dmx on the copy stream,
         // beside the next kernels, so a small batch's solve does not carry it either)
-        double* xw = (ctx->d_xw && (ctx->cov_defer == 2 || (ctx->cov_defer == 1 && (ctx->ninst >= 16 || ctx->lazy))))
-                         ? ctx->d_xw : nullptr;
-        // (no event on the solve's dispatch: lazy copy-stream readers of the step are enqueued
-        // at its end (flush_cq); in a graph capture a plain ev_solved record after the solve is
-        // the capture's cross-stream edge.  Round 4 carried ev_solved on this packet: ~5 us of
-        // idle stream after the solve in every step.)
+        p.xw = ctx->d_xw && (ctx->cov_defer == 2 || (ctx->cov_defer == 1 && (ctx->ninst >= 16 || ctx->lazy)));
+        p.lds_dyn = pl.fuse_sigma ? std::max(p.lds_x, p.lds_s) : p.lds_x;
         // pint_fit_step_apply: the apply at the end of the solve when every instance is solved
         // here on the generated-Fourier path (whose Woodbury Sigma does not read F0 from the
-        // table the apply rewrites)
-        double* apply_tab = nullptr;
-        InstConst* apply_ic = nullptr;
-        size_t lds_dyn = fuse_sigma ? std::max(lds_x, lds_s) : lds_x;
-        if (ctx->apply_req && Ks == 0 && !side_sigma && !do_sigma) {
-            bool ok = true;
-            int maxts = 0;
-            for (int pi : ctx->upsr) {
-                const PsrHost& ph = ctx->psrs[pi];
-                ok = ok && cmp && ph.dev.dsplit && ph.dev.vg;
-                maxts = std::max(maxts, ph.spec.tstride);
-            }
-            // the staging region follows each instance's own solve data (lds_x bounds it)
-            if (ok && lds_x + apply_tail_lds(maxts) <= 160 * 1024 - 512) {
-                apply_tab = ctx->d_tables;
-                apply_ic = ctx->d_ic;
-                lds_dyn = std::max(lds_dyn, lds_x + apply_tail_lds(maxts));
-                ctx->apply_done = true;
-                ctx->tables_fresh = false;
-            }
+        // table the apply rewrites); the staging region follows each instance's own solve data
+        // (lds_x bounds it)
+        const size_t lds_apply = p.lds_x + apply_tail_lds(s.maxts);
+        if (apply_req && all_dmx && !pl.side_sigma && !pl.do_sigma && s.all_vg && lds_apply <= FIT_LDS - 512) {
+            p.apply_tail = true;
+            p.lds_dyn = std::max(p.lds_dyn, lds_apply);
         }
         // the build phase (norms, S and U, S -= U U^T, b'_d) spread over the chip by k_schur
         // when the solve exports to xw (deferred solves); PINT_SCHUR=0 keeps it in the solve
-        int pre = 0;
-        if (xw && ctx->schur) {
-            int mnb = 0, mnk = 0;
-            for (int pi : ctx->upsr) {
-                const PsrDev& pd = ctx->psrs[pi].dev;
-                if (!pd.dsplit) continue;
-                const int kd = mode == 0 ? pd.red0c : pd.Kd, nbd = (kd + 15) / 16;
-                mnb = std::max(mnb, nbd * (nbd + 1) / 2);
-                mnk = std::max(mnk, (pd.ndc + 15) / 16);
-            }
-            if (mnb > 0) {
-                hipLaunchKernelGGL(k_schur, dim3(mnb, ctx->ninst), dim3(SCHUR_T), schur_lds(mnk), ctx->stream,
-                                   (const PsrDev*)ctx->d_psrs, (const InstDev*)ctx->d_inst, (const double*)ctx->d_G,
-                                   (const double*)ctx->d_colsq, ctx->nsplit, mode, (const double*)ctx->d_Sd,
-                                   (const double*)ctx->d_DD, (const double*)ctx->d_DCS, xw);
-                HIPCHK(hipGetLastError());
-                pre = 1;
-            }
-        }
+        p.pre = p.xw && ctx->schur && s.nbd > 0;
+        p.mnb = s.nbd * (s.nbd + 1) / 2;
+        p.lds_schur = schur_lds(s.nbk);
         // 8 waves (256 VGPRs per lane) when the dense block fits them (nbd <= 8 and, for the
         // fused Woodbury Sigma, nbs <= 9): the 16-wave form's 128-VGPR budget made the
         // diagonal factor spill its pivot columns to SGPRs and sink each column's updates to
         // its pivot, serialising them (a chain of j FMAs before pivot j)
-        int mnbd = 0;
-        for (int pi : ctx->upsr) {
-            const PsrDev& pd = ctx->psrs[pi].dev;
-            if (pd.dsplit) mnbd = std::max(mnbd, ((mode == 0 ? pd.red0c : pd.Kd) + 15) / 16);
-        }
-        const bool w8 = ctx->solve_w8 && mnbd <= 8 && (!fuse_sigma || nbs_sig <= 9);
-#define PINT_SOLVE_DMX(NWS)                                                                                          \
-        hipExtLaunchKernelGGL((k_solve_dmx<NWS>), dim3(ctx->ninst * (fuse_sigma ? 2 : 1)), dim3(NWS * 64),           \
-                              (uint32_t)lds_dyn, ctx->stream, nullptr, nullptr, 0u,                                  \
-                              (const PsrDev*)ctx->d_psrs, (const InstDev*)ctx->d_inst, (const double*)ctx->d_tables, \
-                              (const double*)ctx->d_G, (const double*)ctx->d_colsq, ctx->nsplit, mode,               \
-                              (const double*)ctx->d_Sd, (const double*)ctx->d_DD, (const double*)ctx->d_DCS,         \
-                              ctx->d_dpars, ctx->d_errs, ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status,     \
-                              fuse_sigma, ctx->refine, xw, ones, apply_tab, apply_ic, ctx->apply_lam, pre,           \
-                              ctx->la_chol)
-        if (w8) PINT_SOLVE_DMX(8); else PINT_SOLVE_DMX(16);
-#undef PINT_SOLVE_DMX
-        HIPCHK(hipGetLastError());
-        pl.solve_dmx_waves = w8 ? 8 : 16;
-        pl.schur = pre;
-        pl.cov_deferred = xw != nullptr;
-        ctx->cov_pending = xw != nullptr;
-        ctx->cov_mode = mode;
-        ctx->cov_lds = lds_x;
+        p.w8 = ctx->solve_w8 && s.nbd <= 8 && (!pl.fuse_sigma || s.nbs_sig <= 9);
+        pl.solve_dmx_waves = p.w8 ? 8 : 16;
+        pl.schur = p.pre;
+        pl.cov_deferred = p.xw;
     }
-    if (skip && Ks == 0) {
-        // every instance went through k_solve_dmx
-    } else if (!col_solve) {
-        const int ldsw = nbx * (nbx + 1) / 2 * 256 + 2 * 16 * nbx;  // doubles per instance
-        const int ldsw1 = ldsw + 3 * 16 * nbx;  // (+ the three scratch vectors: one-wave form)
-        size_t lds_b = sizeof(double) * (size_t)ldsw;
-        // K <= 32 (a grid's points): a wave per instance, four per workgroup -- the 4-wave
-        // form spent ~27 us of barriers and idle waves on each such instance
-        if (nbx <= 1 && ctx->small && ctx->lane_solve && !skip && Ks <= 8) {
-            // K <= 8 (a grid's points): a lane per instance
-            const int KT = Ks <= 4 ? 4 : 8;
-            pl.solve = KT == 4 ? PINT_PLAN_SOLVE_LANES4 : PINT_PLAN_SOLVE_LANES8;
-            if (KT == 4)
-                hipLaunchKernelGGL(k_solve_lanes<4>, dim3((ctx->ninst + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_psrs,
-                                   ctx->d_inst, ctx->d_G, ctx->d_colsq, ctx->nsplit, mode, ctx->d_dpars, ctx->d_errs,
-                                   ctx->d_cov, ctx->d_chi2lin, ctx->d_status, ctx->refine, ctx->ninst);
-            else
-                hipLaunchKernelGGL(k_solve_lanes<8>, dim3((ctx->ninst + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_psrs,
-                                   ctx->d_inst, ctx->d_G, ctx->d_colsq, ctx->nsplit, mode, ctx->d_dpars, ctx->d_errs,
-                                   ctx->d_cov, ctx->d_chi2lin, ctx->d_status, ctx->refine, ctx->ninst);
-        } else if (nbx <= 2 && ctx->small)
-            hipLaunchKernelGGL(k_solve_blk<1>, dim3((ctx->ninst + 3) / 4), dim3(256), 4 * sizeof(double) * ldsw1,
-                               ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_tables, ctx->d_G, ctx->d_colsq,
-                               ctx->nsplit, mode, cmp, ctx->d_Sd, ctx->d_DD, ctx->d_DCS, ctx->d_dpars, ctx->d_errs,
-                               ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, skip, ctx->d_rscr, ctx->refine,
-                               ctx->ninst, ldsw1);
-        else if (nbx <= 5)
-            hipLaunchKernelGGL(k_solve_blk<4>, dim3(ctx->ninst), dim3(256), lds_b, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_tables, ctx->d_G, ctx->d_colsq, ctx->nsplit, mode, cmp, ctx->d_Sd, ctx->d_DD,
-                               ctx->d_DCS, ctx->d_dpars, ctx->d_errs,
-                               ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, skip, ctx->d_rscr, ctx->refine,
-                               ctx->ninst, ldsw);
-        else
-            hipLaunchKernelGGL(k_solve_blk<16>, dim3(ctx->ninst), dim3(1024), lds_b, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_tables, ctx->d_G, ctx->d_colsq, ctx->nsplit, mode, cmp, ctx->d_Sd, ctx->d_DD,
-                               ctx->d_DCS, ctx->d_dpars, ctx->d_errs,
-                               ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, skip, ctx->d_rscr, ctx->refine,
-                               ctx->ninst, ldsw);
-        if (!pl.solve)
-            pl.solve = (nbx <= 2 && ctx->small) ? PINT_PLAN_SOLVE_BLK1
-                                                : (nbx <= 5 ? PINT_PLAN_SOLVE_BLK4 : PINT_PLAN_SOLVE_BLK16);
-    } else {  // (its LDS budget was checked before the first launch)
-        hipLaunchKernelGGL(k_solve, dim3(ctx->ninst), dim3(SOLVE_T), lds_col, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                           ctx->d_tables, ctx->d_G, ctx->d_colsq, ctx->nsplit, nparts, mode, cmp, ctx->d_Sd, ctx->d_DD,
-                           ctx->d_DCS, ctx->d_work, ctx->d_dpars,
-                           ctx->d_errs, ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, skip, do_sigma, ones);
-        pl.solve = PINT_PLAN_SOLVE_COLUMN;
+    p.ldsw = nbx * (nbx + 1) / 2 * 256 + 2 * 16 * nbx;
+    p.ldsw1 = p.ldsw + 3 * 16 * nbx;
+    if (all_dmx) pl.solve = PINT_PLAN_SOLVE_NONE;  // every instance goes through k_solve_dmx
+    else if (col_solve) pl.solve = PINT_PLAN_SOLVE_COLUMN;
+    // K <= 8 (a grid's points): a lane per instance
+    else if (nbx <= 1 && ctx->small && ctx->lane_solve && !p.skip && Ks <= 8)
+        pl.solve = Ks <= 4 ? PINT_PLAN_SOLVE_LANES4 : PINT_PLAN_SOLVE_LANES8;
+    // K <= 32 (a grid's points): a wave per instance, four per workgroup -- the 4-wave
+    // form spent ~27 us of barriers and idle waves on each such instance
+    else if (nbx <= 2 && ctx->small) pl.solve = PINT_PLAN_SOLVE_BLK1;
+    else pl.solve = nbx <= 5 ? PINT_PLAN_SOLVE_BLK4 : PINT_PLAN_SOLVE_BLK16;
+    return p;
+}
+
+// ---- the launch stages, in stream order ----
+static int launch_ecorr(pint_ctx* ctx, const FitPlan& p) {
+    if (!p.ecorr) return PINT_OK;
+    if (any_copy_pend(ctx)) {  // the copy stream's noise realisations read esum / eD
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied, 0));
+        clear_copy_pend(ctx);
+    }
+    hipLaunchKernelGGL(k_ecorr, dim3((ctx->max_nep + 3) / 4, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                       ctx->d_inst, ctx->d_M, ctx->d_rt, ctx->d_esum, ctx->d_eD, ctx->d_eW, ctx->m_compact,
+                       ctx->d_dmxv, ctx->d_eC);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+// PhaseOffset with a frozen PHOFF and correlated noise: the Woodbury ones row
+static int launch_onesrow(pint_ctx* ctx, const FitPlan& p) {
+    if (!p.ones) return PINT_OK;
+    hipLaunchKernelGGL(k_onesrow, dim3(ctx->ninst), dim3(64), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_esum,
+                       ctx->d_eD, ctx->d_eW, ctx->d_eC, ctx->m_compact, ctx->d_M, ctx->d_ones);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+static int launch_dmx_rows(pint_ctx* ctx, const FitPlan& p) {
+    if (!p.pub.dmx_rows) return PINT_OK;
+    const dim3 grid(ctx->max_ndc, ctx->ninst);
+    hipLaunchKernelGGL(k_dmx_rows, grid, dim3(256), p.lds_rows, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_M,
+                       ctx->d_rt, ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
+    HIPCHK(hipGetLastError());
+    if (p.pub.dmx) {
+        hipLaunchKernelGGL(k_dmx, grid, dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_M, ctx->d_rt,
+                           ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
+        HIPCHK(hipGetLastError());
+    }
+    if (p.pub.ecorr_dmx) {
+        hipLaunchKernelGGL(k_ecorr_dmx, grid, dim3(64), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_esum,
+                           ctx->d_eD, ctx->d_eC, ctx->d_Sd, ctx->d_DD);
+        HIPCHK(hipGetLastError());
+    }
+    return PINT_OK;
+}
+
+// k_gram_s / k_gram over the launch groups; opens the Gram's marker-packet timing
+static int launch_gram(pint_ctx* ctx, const FitPlan& p) {
+    if (p.gram_mark) record(ctx, 12);
+    const int cmp = ctx->m_compact;
+    const std::vector<KpGroup>& groups = cmp ? ctx->kp_groups_c : ctx->kp_groups;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const KpGroup& kg = groups[g];
+        const FitPlan::GramGroup& pg = p.gram[g];
+        const InstDev* di = (cmp ? ctx->d_inst_sorted_c : ctx->d_inst_sorted) + kg.first;
+        if (!pg.kern)
+            hipLaunchKernelGGL(k_gram_s, dim3(ctx->nsplit, (kg.count + 3) / 4), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                               di, kg.count, ctx->d_M, ctx->d_rt, ctx->nsplit, cmp, ctx->d_G, ctx->d_colsq);
+        for (int virt = 0; virt < 2; virt++) {  // (the ECORR variant: one more part, in one block row)
+            const GramKernel kern = virt ? pg.kern_ecorr : pg.kern;
+            if (kern)
+                hipLaunchKernelGGL(kern, dim3(virt ? 1 : ctx->nsplit, kg.count), dim3(GTHREADS), pg.lds, ctx->stream,
+                                   ctx->d_psrs, di, ctx->d_M, ctx->d_rt, ctx->d_esum, ctx->d_eD, ctx->nsplit, cmp,
+                                   ctx->d_G, ctx->d_colsq);
+        }
     }
     HIPCHK(hipGetLastError());
-    ctx->plan = pl;
+    return PINT_OK;
+}
+
+// k_gram_v over its launch groups; closes the Gram's timing
+static int launch_gram_v(pint_ctx* ctx, const FitPlan& p) {
+    if (p.ext_t)  // (the timing events are created at first use)
+        for (int i : {12, 13})
+            if (!ctx->ev[i]) HIPCHK(hipEventCreate(&ctx->ev[i]));
+    const GvResid gvr{ctx->d_rp, ctx->d_ftay, ctx->d_rpart, ctx->r2_pending ? 1 : 0, ctx->efz ? ctx->d_epart : nullptr};
+    const size_t ng = p.vgp ? ctx->kp_groups_v.size() : 0;
+    for (size_t g = 0; g < ng; g++) {
+        const KpGroup& kg = ctx->kp_groups_v[g];
+        hipEvent_t e0 = (p.ext_t && g == 0) ? ctx->ev[12] : nullptr;
+        hipEvent_t e1 = (p.ext_t && g + 1 == ng) ? ctx->ev[13] : nullptr;
+        hipExtLaunchKernelGGL(p.gramv[g].kern, dim3(ctx->nsplit, kg.count), dim3(GW * 64), p.gramv[g].lds, ctx->stream,
+                              e0, e1, 0u, (const PsrDev*)ctx->d_psrs, (const InstDev*)(ctx->d_inst_sorted_v + kg.first),
+                              (const double*)ctx->d_M, (const double*)ctx->d_rt, (const double*)ctx->d_dmxv, ctx->nsplit,
+                              ctx->d_G, ctx->d_Sdp, ctx->d_colsq, ctx->d_TSp, ctx->d_BFp, ctx->gvdbg, gvr);
+    }
+    if (p.ext_t) ctx->rec[12] = ctx->rec[13] = true;
+    else if (p.gram_mark) record(ctx, 13);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+static int launch_greduce(pint_ctx* ctx, const FitPlan& p) {
+    if (!p.pub.greduce) return PINT_OK;
+    const GredArgs gra{ctx->nsplit, p.nparts, ctx->m_compact, ctx->vb_on, ctx->d_G, ctx->d_colsq, ctx->d_Sdp,
+                       ctx->d_dmxv, ctx->d_Sd, ctx->d_DD, ctx->d_DCS, ctx->d_BFp};
+    // (round 4: the column sums of squares on threads of their own, beside the Gram's
+    // chains, measured no faster -- 11.3-11.9 vs 10.5-10.9 us at 9 pulsars)
+    record(ctx, 14);
+    hipLaunchKernelGGL(k_greduce, dim3(p.nbg + (p.vgp ? (ctx->max_ndc + 3) / 4 : 0), ctx->ninst), dim3(256), 0,
+                       ctx->stream, ctx->d_psrs, ctx->d_inst, p.nbg, gra);
+    HIPCHK(hipGetLastError());
+    record(ctx, 15);
+    return PINT_OK;
+}
+
+static int launch_wb_gram(pint_ctx* ctx, const FitPlan& p) {
+    if (!p.pub.wb_gram) return PINT_OK;
+    if (int rc = ensure_ic_solar_wind(ctx)) return rc;
+    hipLaunchKernelGGL(k_wb_gram, dim3(ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_tables,
+                       ctx->d_ic, ctx->nsplit, ctx->d_G, ctx->d_colsq, ctx->d_Sd, ctx->d_DD, ctx->d_DCS);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+// k_sigma on the side stream, after the Gram
+static int launch_side_sigma(pint_ctx* ctx, const FitPlan& p) {
+    if (!p.pub.side_sigma) return PINT_OK;
+    HIPCHK(hipEventRecord(ctx->ev_gram, ctx->stream));
+    HIPCHK(hipStreamWaitEvent(ctx->sstream, ctx->ev_gram, 0));
+    const int nw = p.pub.sigma_waves;
+    const auto kern = nw == 4 ? k_sigma<4> : k_sigma<16>;
+    hipLaunchKernelGGL(kern, dim3(ctx->ninst), dim3(nw * 64), p.lds_s, ctx->sstream, ctx->d_psrs, ctx->d_inst,
+                       ctx->d_tables, ctx->d_G, ctx->m_compact, ctx->d_Sd, ctx->d_DD, ctx->d_sigL, ctx->d_status,
+                       p.ones ? ctx->d_ones : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_sigma, ctx->sstream));
+    ctx->sigma_pending = true;
+    return PINT_OK;
+}
+
+// k_schur + k_solve_dmx for the instances on the compact DMX layout; leaves k_cov_dmx's
+// launch state for pint_read_step.  lam: the fused apply's step length (p.apply_tail)
+static int launch_solve_dmx(pint_ctx* ctx, const FitPlan& p, double lam) {
+    ctx->cov_pending = false;
+    if (!p.skip) return PINT_OK;
+    double* xw = p.xw ? ctx->d_xw : nullptr;
+    if (p.pre) {
+        hipLaunchKernelGGL(k_schur, dim3(p.mnb, ctx->ninst), dim3(SCHUR_T), p.lds_schur, ctx->stream,
+                           (const PsrDev*)ctx->d_psrs, (const InstDev*)ctx->d_inst, (const double*)ctx->d_G,
+                           (const double*)ctx->d_colsq, ctx->nsplit, p.mode, (const double*)ctx->d_Sd,
+                           (const double*)ctx->d_DD, (const double*)ctx->d_DCS, xw);
+        HIPCHK(hipGetLastError());
+    }
+    // (no event on the solve's dispatch: lazy copy-stream readers of the step are enqueued
+    // at its end (flush_cq); in a graph capture a plain ev_solved record after the solve is
+    // the capture's cross-stream edge.  Round 4 carried ev_solved on this packet: ~5 us of
+    // idle stream after the solve in every step.)
+    const int fuse = p.pub.fuse_sigma, nw = p.w8 ? 8 : 16;
+    const auto kern = p.w8 ? k_solve_dmx<8> : k_solve_dmx<16>;
+    hipExtLaunchKernelGGL(kern, dim3(ctx->ninst * (fuse ? 2 : 1)), dim3(nw * 64),
+                          (uint32_t)p.lds_dyn, ctx->stream, nullptr, nullptr, 0u, (const PsrDev*)ctx->d_psrs,
+                          (const InstDev*)ctx->d_inst, (const double*)ctx->d_tables, (const double*)ctx->d_G,
+                          (const double*)ctx->d_colsq, ctx->nsplit, p.mode, (const double*)ctx->d_Sd,
+                          (const double*)ctx->d_DD, (const double*)ctx->d_DCS, ctx->d_dpars, ctx->d_errs, ctx->d_cov,
+                          ctx->d_chi2lin, ctx->d_sigL, ctx->d_status, fuse, ctx->refine, xw,
+                          (const double*)(p.ones ? ctx->d_ones : nullptr), p.apply_tail ? ctx->d_tables : nullptr,
+                          p.apply_tail ? ctx->d_ic : nullptr, lam, (int)p.pre, ctx->la_chol);
+    HIPCHK(hipGetLastError());
+    if (p.apply_tail) ctx->tables_fresh = false;
+    ctx->cov_pending = p.xw;
+    ctx->cov_mode = p.mode;
+    ctx->cov_lds = p.lds_x;
+    return PINT_OK;
+}
+
+// the general solve of the instances k_solve_dmx did not take
+static int launch_solve(pint_ctx* ctx, const FitPlan& p) {
+    const int cmp = ctx->m_compact, ninst = ctx->ninst, solve = p.pub.solve;
+    if (solve == PINT_PLAN_SOLVE_LANES4 || solve == PINT_PLAN_SOLVE_LANES8) {
+        const auto kern = solve == PINT_PLAN_SOLVE_LANES4 ? k_solve_lanes<4> : k_solve_lanes<8>;
+        hipLaunchKernelGGL(kern, dim3((ninst + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_G,
+                           ctx->d_colsq, ctx->nsplit, p.mode, ctx->d_dpars, ctx->d_errs, ctx->d_cov, ctx->d_chi2lin,
+                           ctx->d_status, ctx->refine, ninst);
+    } else if (solve == PINT_PLAN_SOLVE_COLUMN) {  // (its LDS budget was checked by the planner)
+        hipLaunchKernelGGL(k_solve, dim3(ninst), dim3(SOLVE_T), p.lds_col, ctx->stream, ctx->d_psrs, ctx->d_inst,
+                           ctx->d_tables, ctx->d_G, ctx->d_colsq, ctx->nsplit, p.nparts, p.mode, cmp, ctx->d_Sd, ctx->d_DD,
+                           ctx->d_DCS, ctx->d_work, ctx->d_dpars, ctx->d_errs, ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL,
+                           ctx->d_status, p.skip, p.pub.do_sigma, p.ones ? ctx->d_ones : nullptr);
+    } else if (solve != PINT_PLAN_SOLVE_NONE) {
+        // one wave per instance and four instances per workgroup, or a workgroup of 4 or 16 waves
+        const bool one = solve == PINT_PLAN_SOLVE_BLK1;
+        const int ldsw = one ? p.ldsw1 : p.ldsw;
+        const auto kern = one ? k_solve_blk<1> : (solve == PINT_PLAN_SOLVE_BLK4 ? k_solve_blk<4> : k_solve_blk<16>);
+        hipLaunchKernelGGL(kern, dim3(one ? (ninst + 3) / 4 : ninst), dim3(solve == PINT_PLAN_SOLVE_BLK16 ? 1024 : 256),
+                           sizeof(double) * (size_t)ldsw * (one ? 4 : 1), ctx->stream, ctx->d_psrs, ctx->d_inst,
+                           ctx->d_tables, ctx->d_G, ctx->d_colsq, ctx->nsplit, p.mode, cmp, ctx->d_Sd, ctx->d_DD,
+                           ctx->d_DCS, ctx->d_dpars, ctx->d_errs, ctx->d_cov, ctx->d_chi2lin, ctx->d_sigL, ctx->d_status,
+                           p.skip, ctx->d_rscr, ctx->refine, ninst, ldsw);
+    }
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+// Gram + solve for every instance; apply_lam: also tables += *apply_lam * step when the solve
+// can carry it (*applied tells), pint_fit_step_apply.
+static int fit_step_impl(pint_ctx* ctx, int mode, const double* apply_lam, bool* applied) {
+    if (flush_restore(ctx)) return PINT_E_HIP;
+    hipSetDevice(ctx->device);
+    // deferred reads of this slot's outputs enqueued since the last step_end go first (this
+    // solve rewrites them)
+    if (int rc = flush_cq_now(ctx)) return rc;
+    if (ctx->r2_pending && !can_defer_r2(ctx)) flush_r2(ctx);  // (a kernel below reads d_rt)
+    const bool sampled = ctx->timing_every <= 1 || (ctx->gram_calls % ctx->timing_every) == 0;
+    const FitPlan p = plan_fit_step(ctx, mode, apply_lam != nullptr, sampled);
+    ctx->plan = pint_plan_t{};
+    if (p.err) {
+        ctx->err = p.err;
+        return PINT_E_INVALID;
+    }
+    if (ctx->timing_every > 1) ctx->gram_calls++;
+    if (ctx->sigma_pending) {  // the previous k_sigma reads the Gram buffer this step overwrites
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));
+        ctx->sigma_pending = false;
+    }
+    int rc;
+    record(ctx, 6);
+    if ((rc = launch_ecorr(ctx, p)) || (rc = launch_onesrow(ctx, p)) || (rc = launch_dmx_rows(ctx, p)) ||
+        (rc = launch_gram(ctx, p)) || (rc = launch_gram_v(ctx, p)) || (rc = launch_greduce(ctx, p)) ||
+        (rc = launch_wb_gram(ctx, p)))
+        return rc;
+    record(ctx, 7);
+    if ((rc = launch_side_sigma(ctx, p))) return rc;
+    if (ctx->copy_pend[ctx->slot]) {  // this slot's outputs may still be in flight to the host
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied, 0));  // (the latest copies: covers them)
+        clear_copy_pend(ctx);
+    }
+    if ((rc = launch_solve_dmx(ctx, p, apply_lam ? *apply_lam : 1.0)) || (rc = launch_solve(ctx, p))) return rc;
+    if (applied) *applied = p.apply_tail;
+    ctx->plan = p.pub;
     record(ctx, 8);
     if (ctx->capturing) HIPCHK(hipEventRecord(ctx->ev_solved, ctx->stream));
     if (ctx->lazy) return PINT_OK;
-    int rc = check_status(ctx);
+    rc = check_status(ctx);
     update_timings(ctx);
     return rc;
+}
+
+int pint_fit_step(pint_ctx* ctx, int mode) {
+    if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
+    return fit_step_impl(ctx, mode, nullptr, nullptr);
 }
 
 // The SVD path of the fitters (k_eig) on the Gram of the last pint_fit_step: replaces the
@@ -9845,28 +9901,32 @@ int pint_solve_eig(pint_ctx* ctx, int mode, const double* threshold, int32_t* nd
 int pint_read_step(pint_ctx* ctx, double* dpars, double* errs, double* cov, double* chi2lin) {
     if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
     hipSetDevice(ctx->device);
+    // the DMX-eliminated solve's W, DMX errors, covariance: k_cov_dmx, with the launch state of
+    // now (a lazy read runs it later)
+    // (round 4: capping it at ~half the CUs, beside the next pipelined step's evaluation,
+    // looked 7 % faster in one A/B sweep and not at all in a second -- the 68-pulsar step is
+    // bimodal run to run on one box, 0.38 or 0.41 ms; PINT_COV_WG sets a fixed count)
+    static const int cov_env = getenv("PINT_COV_WG") ? atoi(getenv("PINT_COV_WG")) : 0;
+    const bool cov_run = (cov || errs) && ctx->cov_pending;
+    auto launch_cov_dmx = [ctx, grid = dim3(ctx->ninst, cov ? (cov_env > 0 ? cov_env : COV_WG) : 1), lds = ctx->cov_lds,
+                           psrs = ctx->d_psrs, insts = ctx->d_inst, xw = ctx->d_xw, mode = ctx->cov_mode,
+                           d_cv = cov ? ctx->d_cov : nullptr, d_er = ctx->d_errs](hipStream_t st) -> int {
+        hipLaunchKernelGGL(k_cov_dmx<16>, grid, dim3(1024), lds, st, psrs, insts, xw, mode, d_cv, d_er);
+        HIPCHK(hipGetLastError());
+        return PINT_OK;
+    };
     if (ctx->lazy && !ctx->capturing) {
         // lazy: k_cov_dmx and the copies go on the copy stream at the step's end (flush_cq),
         // overlapped with the next step's kernels; the caller's buffers (pinned:
         // pint_host_alloc) are valid after pint_check() / pint_check_step().  The slot's
         // output buffers and the launch state are taken now.
-        const bool cov_run = (cov || errs) && ctx->cov_pending;
-        static const int cov_env = getenv("PINT_COV_WG") ? atoi(getenv("PINT_COV_WG")) : 0;
-        const int cov_wg = cov_env > 0 ? cov_env : COV_WG;
-        const int ninst = ctx->ninst, mode = ctx->cov_mode;
-        const size_t lds = ctx->cov_lds;
+        const int ninst = ctx->ninst;
         const long tc = ctx->tot_c, tcv = ctx->tot_cv;
         double *d_dp = ctx->d_dpars, *d_er = ctx->d_errs, *d_cv = ctx->d_cov, *d_cl = ctx->d_chi2lin;
-        const double* d_xw = ctx->d_xw;
-        const PsrDev* psrs = ctx->d_psrs;
-        const InstDev* insts = ctx->d_inst;
         ctx->cq.push_back([=]() -> int {
-            hipStream_t st = ctx->cstream;
             HostLap lap{"read_step op"};
             if (cov_run) {
-                hipLaunchKernelGGL(k_cov_dmx<16>, dim3(ninst, cov ? cov_wg : 1), dim3(1024), lds, st, psrs, insts, d_xw,
-                                   mode, cov ? d_cv : nullptr, d_er);
-                HIPCHK(hipGetLastError());
+                if (int rc = launch_cov_dmx(ctx->cstream)) return rc;
                 lap("k_cov_dmx launch");
             }
             if (int rc = export_seg(ctx, dpars, d_dp, tc)) return rc;
@@ -9883,16 +9943,8 @@ int pint_read_step(pint_ctx* ctx, double* dpars, double* errs, double* cov, doub
     // cross-stream edge of the graph), or on the kernel stream
     hipStream_t st = ctx->lazy ? ctx->cstream : ctx->stream;
     if (ctx->lazy) HIPCHK(hipStreamWaitEvent(ctx->cstream, ctx->ev_solved, 0));
-    if ((cov || errs) && ctx->cov_pending) {  // the DMX-eliminated solve's W, DMX errors, covariance
-        // (round 4: capping it at ~half the CUs, beside the next pipelined step's evaluation,
-        // looked 7 % faster in one A/B sweep and not at all in a second -- the 68-pulsar step is
-        // bimodal run to run on one box, 0.38 or 0.41 ms; PINT_COV_WG sets a fixed count)
-        static const int cov_env = getenv("PINT_COV_WG") ? atoi(getenv("PINT_COV_WG")) : 0;
-        const int cov_wg = cov_env > 0 ? cov_env : COV_WG;
-        hipLaunchKernelGGL(k_cov_dmx<16>, dim3(ctx->ninst, cov ? cov_wg : 1), dim3(1024), ctx->cov_lds, st,
-                           ctx->d_psrs, ctx->d_inst, ctx->d_xw, ctx->cov_mode, cov ? ctx->d_cov : nullptr,
-                           ctx->d_errs);
-        HIPCHK(hipGetLastError());
+    if (cov_run) {
+        if (int rc = launch_cov_dmx(st)) return rc;
         ctx->cov_pending = cov == nullptr;  // errors only: a later read of the covariance re-runs it
     }
     if (dpars) HIPCHK(d2h(dpars, ctx->d_dpars, sizeof(double) * ctx->tot_c, st));
@@ -9959,19 +10011,12 @@ int pint_apply_step_uniform(pint_ctx* ctx, double lambda_) {
 // pint_noise_resids) read the step, not the tables, so they may follow.
 int pint_fit_step_apply(pint_ctx* ctx, int mode, double lambda_) {
     if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
-    ctx->apply_req = true;
-    ctx->apply_lam = lambda_;
-    ctx->apply_done = false;
-    const int rc = pint_fit_step(ctx, mode);
-    ctx->apply_req = false;
-    if (rc != PINT_OK) return rc;
-    if (ctx->apply_done) {
-        ctx->apply_done = false;
-        ctx->ic_valid = true;
-        ctx->phases_valid = false;
-        return PINT_OK;
-    }
-    return pint_apply_step_uniform(ctx, lambda_);
+    bool applied = false;
+    if (int rc = fit_step_impl(ctx, mode, &lambda_, &applied)) return rc;
+    if (!applied) return pint_apply_step_uniform(ctx, lambda_);
+    ctx->ic_valid = true;
+    ctx->phases_valid = false;
+    return PINT_OK;
 }
 
 // Parameter tables resident on the device: pint_save_tables snapshots the current tables,

@@ -530,6 +530,53 @@ def test_wideband_step_off_the_compact_layout_is_refused(what, toa_sets):
         s.close()
 
 
+def test_a_refused_step_changes_no_state(toa_sets):
+    """A refused pint_fit_step between two valid ones (the refusal test's 5-free-bin wideband
+    pulsar, the DM rows switched on for the refused call only): the plan it leaves is all-zero,
+    not the previous step's, and the next valid step's outputs are bit for bit those of a fresh
+    session that never saw the refusal."""
+    from pint_amd import _lib
+    from pint_amd.engine import Session, build_layout, pack_table
+    c = WB.case("wb_refused", 6, 5, 0, "n300", dm_free=("DM1",))
+    toas, model, z, _ = case_data(c, toa_sets)
+
+    def valid_step(s):
+        s.fit_step(1)
+        dp, er, cov, cl = s.read_step()
+        return [np.array(dp[0]), np.array(er[0]), np.array(cov[0]), np.array(cl)], s.last_plan()
+
+    def session():
+        s = Session()
+        lay = s.add(build_layout(model, toas, track_mode="nearest"))
+        s.set_instances([(lay, pack_table(lay))])
+        s.set_wideband(lay)
+        s.eval(want_M=Session.FIT)
+        s.debug_set_resids([1e-6 * z])
+        return s
+    s = session()
+    try:
+        before, plan = valid_step(s)
+        assert any(v for k, v in plan.items() if k != "solve") and np.all(np.isfinite(before[0]))
+        s.set_wbfit(True)
+        with pytest.raises(_lib.PintError) as e:
+            s.fit_step(1)
+        assert e.value.code == _lib.PINT_E_INVALID
+        refused = s.last_plan()
+        assert refused["solve"] == "none" and not any(v for k, v in refused.items() if k != "solve")
+        s.set_wbfit(False)
+        after, plan_after = valid_step(s)
+    finally:
+        s.close()
+    s = session()
+    try:
+        fresh, plan_fresh = valid_step(s)
+    finally:
+        s.close()
+    assert plan_after == plan_fresh == plan
+    for a, b, f in zip(before, after, fresh):
+        assert a.tobytes() == f.tobytes() and b.tobytes() == f.tobytes()
+
+
 @pytest.fixture(scope="module")
 def e2e_toas():
     """Fake TOAs zeroed on each end-to-end case's own model (so that the step is of the order
