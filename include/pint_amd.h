@@ -658,6 +658,16 @@ int pint_graph_launch(pint_ctx *ctx);
                                    batch (same pulsar, point count and options) and only formed new tables */
 #define PINT_QUERY_NPLGLS 6     /* k_point_lnl_gls launches of this context (pint_point_lnlike_gls): a call refused
                                    before any launch leaves it unchanged */
+#define PINT_QUERY_RESID_PATH 7 /* PINT_RESID_* bits: what the last pint_eval's residual pass launched or left
+                                   pending (a later flush of the deferred second half adds its k_resid2 bit) */
+#define PINT_RESID_EFUSED 1     /* first half in the evaluation's blocks */
+#define PINT_RESID_R1_64 2      /* k_resid1<64> */
+#define PINT_RESID_R1_256 4     /* k_resid1<256> */
+#define PINT_RESID_R12 8        /* k_resid12 */
+#define PINT_RESID_R2_64 16     /* k_resid2<64> */
+#define PINT_RESID_R2_256 32    /* k_resid2<256> */
+#define PINT_RESID_TILES 64     /* k_resid2 formed the Woodbury trig tiles */
+#define PINT_RESID_DEFERRED 128 /* second half left to k_gram_v (or to the first reader of the residuals) */
 int pint_query(pint_ctx *ctx, int key);
 /* The launch plan of the last pint_fit_step (host bookkeeping, no reference counterpart): which
  * kernel instantiations the call enqueued, as the dispatcher chose them from the batch's padded

@@ -6841,6 +6841,7 @@ struct pint_ctx {
     int prep_lanes = 1;  // PINT_PREP_LANES: lane-per-instance k_prep / k_apply for small tables
     int fuse_r2 = 1;     // PINT_FUSE_R2: the fit layout's k_resid2 folded into k_gram_v's staging
     bool r2_pending = false;  // k_resid2 of the last pass deferred (the Gram formed its residuals)
+    int resid_path = 0;  // PINT_RESID_* of the last pint_eval's residual pass (PINT_QUERY_RESID_PATH)
     bool grid_valid = false;  // the batch is pint_set_grid's: grid_psr's points, options grid_opts
     std::vector<double> grid_spec_host;  // pint_set_grid's spec, kept while its upload may run
     int grid_psr = -1;
@@ -9044,14 +9045,18 @@ static void launch_apply(pint_ctx* ctx, const double* lam, double lam_u) {
 static void launch_resid2(pint_ctx* ctx, bool wt) {
     const size_t wlds = wt ? sizeof(double) * std::max((RES_BT / 64) * 32 * WT_CS2, 4 * 256) : 0;
     const double* ep = ctx->efz ? ctx->d_epart : nullptr;
-    if (!ctx->efz && ctx->small && ctx->maxn <= RES_SMALLN)
+    if (wt) ctx->resid_path |= PINT_RESID_TILES;
+    if (!ctx->efz && ctx->small && ctx->maxn <= RES_SMALLN) {
+        ctx->resid_path |= PINT_RESID_R2_64;
         hipLaunchKernelGGL(k_resid2<64>, dim3((ctx->nrblk + 3) / 4), dim3(RES_BT), wlds, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_ftay, ctx->d_rt, ctx->d_rp, ctx->d_rpart,
                            wt ? ctx->d_wtile : nullptr, ep);
-    else
+    } else {
+        ctx->resid_path |= PINT_RESID_R2_256;
         hipLaunchKernelGGL(k_resid2<RES_BT>, dim3(ctx->nrblk), dim3(RES_BT), wlds, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_ftay, ctx->d_rt, ctx->d_rp, ctx->d_rpart,
                            wt ? ctx->d_wtile : nullptr, ep);
+    }
 }
 
 // The fit layout's residual pass may leave k_resid2 to the Gram (GvResid) when every instance
@@ -9079,6 +9084,7 @@ int pint_eval(pint_ctx* ctx, int want_M) {
     hipSetDevice(ctx->device);
     if (want_M < 0 || want_M > 2) return PINT_E_INVALID;
     ctx->r2_pending = false;  // (this pass replaces the residuals a deferred k_resid2 would form)
+    ctx->resid_path = 0;
     if (want_M) ctx->m_compact = (want_M == 2) ? 1 : 0;
     // the full and compact layouts place the red-noise columns differently; each is written
     // once after pint_set_instances (M is reallocated there)
@@ -9215,21 +9221,27 @@ int pint_eval(pint_ctx* ctx, int want_M) {
         const bool fused12 = !ctx->efz && ctx->small && ctx->maxn <= RES_SMALLN && !wt && !defer2 && ctx->resid12;
         if (ctx->efz) {
             // (k_resid1's work done by the evaluation's blocks)
+            ctx->resid_path |= PINT_RESID_EFUSED;
         } else if (fused12) {  // one wave per instance does both passes
+            ctx->resid_path |= PINT_RESID_R12;
             hipLaunchKernelGGL(k_resid12, dim3((ctx->nrblk + 3) / 4), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
                                ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay,
                                ctx->d_rt, ctx->d_rp, ctx->d_rpart);
         } else if (ctx->small && ctx->maxn <= RES_SMALLN) {  // a wave per residual block
             const int nb4 = (ctx->nrblk + 3) / 4;
+            ctx->resid_path |= PINT_RESID_R1_64;
             hipLaunchKernelGGL(k_resid1<64>, dim3(nb4), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
                                ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_rp, ctx->d_rpart);
         } else {
+            ctx->resid_path |= PINT_RESID_R1_256;
             hipLaunchKernelGGL(k_resid1<RES_BT>, dim3(ctx->nrblk), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
                                ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_rp,
                                ctx->d_rpart);
         }
-        if (defer2) ctx->r2_pending = true;
-        else if (!fused12) launch_resid2(ctx, wt);
+        if (defer2) {
+            ctx->r2_pending = true;
+            ctx->resid_path |= PINT_RESID_DEFERRED;
+        } else if (!fused12) launch_resid2(ctx, wt);
         // the chi2 partials are summed when the chi2 is read (pint_read_resids) or by k_wsolve,
         // which needs them anyway: no launch of its own in a fit step
         ctx->chi2_pending = true;
@@ -10254,6 +10266,7 @@ int pint_query(pint_ctx* ctx, int key) {
     if (key == PINT_QUERY_WFUSE) return ctx->wfuse ? 1 : 0;
     if (key == PINT_QUERY_NREUSE) return ctx->n_batch_reuse;
     if (key == PINT_QUERY_NPLGLS) return ctx->n_plgls;
+    if (key == PINT_QUERY_RESID_PATH) return ctx->resid_path;
     ctx->err = "unknown query";
     return -PINT_E_INVALID;
 }

@@ -1181,6 +1181,14 @@ class Session:
         PLRedNoise series of at most 63 modes)."""
         return bool(self.L.pint_query(self.ctx, 4))
 
+    RESID_EFUSED, RESID_R1_64, RESID_R1_256, RESID_R12 = 1, 2, 4, 8
+    RESID_R2_64, RESID_R2_256, RESID_TILES, RESID_DEFERRED = 16, 32, 64, 128
+
+    def resid_path(self):
+        """RESID_* bits of what the last eval's residual pass launched or left pending
+        (PINT_QUERY_RESID_PATH); a reader that flushes the deferred second half adds its k_resid2 bit."""
+        return int(self.L.pint_query(self.ctx, 7))
+
     def last_plan(self):
         """The launch plan of the last fit_step (pint_last_plan) as a dict: the k_gram tile
         counts T launched (gram_T), the k_gram_v (key, vb) launches (gram_v), the general solve

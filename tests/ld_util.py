@@ -1,6 +1,6 @@
 """Longdouble linear algebra for the tests' reference solutions (numpy's own solvers drop to
 float64): the solve and the inverse of a stage's linear system, and the weighted Gram and
-Woodbury chi2 the shape sweep compares the kernels against."""
+Woodbury chi2 the shape sweep compares the kernels against, and the host's Fourier columns."""
 import numpy as np
 
 LD = np.longdouble
@@ -65,3 +65,14 @@ def ld_woodbury_chi2(r, sigma, U, phi):
     d = Un.T @ (w * r)
     rNr = np.sum(w * r * r)
     return rNr - d @ ld_solve(Sigma, d), rNr
+
+
+def host_fourier(lay, toas):
+    """sin / cos(2 pi f_k t) in longdouble, t = tdbld * 86400 (noise_model.py:861-880)."""
+    t = np.asarray(toas.tdbld, dtype=LD) * LD(86400)
+    f = np.asarray(lay.red_freq, dtype=LD)
+    F = np.zeros((toas.ntoas, 2 * len(f)), dtype=LD)
+    twopi = 8 * np.arctan(LD(1))  # (np.pi is a double)
+    F[:, ::2] = np.sin(twopi * t[:, None] * f)
+    F[:, 1::2] = np.cos(twopi * t[:, None] * f)
+    return F

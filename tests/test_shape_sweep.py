@@ -153,7 +153,7 @@ import numpy as np
 import pytest
 
 import shape_cases as SC
-from ld_util import LD, ld_gram, ld_inverse, ld_solve, ld_woodbury_chi2
+from ld_util import LD, host_fourier, ld_gram, ld_inverse, ld_solve, ld_woodbury_chi2
 
 pytestmark = pytest.mark.gpu
 
@@ -176,17 +176,6 @@ def toa_sets():
         rng = np.random.default_rng(t.ntoas)
         sets[name] = (t, rng.standard_normal(t.ntoas))
     return sets
-
-
-def host_fourier(lay, toas):
-    """sin / cos(2 pi f_k t) in longdouble, t = tdbld * 86400 (noise_model.py:861-880)."""
-    t = np.asarray(toas.tdbld, dtype=LD) * LD(86400)
-    f = np.asarray(lay.red_freq, dtype=LD)
-    F = np.zeros((toas.ntoas, 2 * len(f)), dtype=LD)
-    twopi = 8 * np.arctan(LD(1))  # (np.pi is a double)
-    F[:, ::2] = np.sin(twopi * t[:, None] * f)
-    F[:, 1::2] = np.cos(twopi * t[:, None] * f)
-    return F
 
 
 def reference(c, toas):
