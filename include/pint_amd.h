@@ -947,6 +947,46 @@ int pint_polyco_eval(pint_ctx *ctx, int64_t n, const double *t_hi, const double 
 int pint_polyco_trig(pint_ctx *ctx, int64_t n, const double *t_hi, const double *t_lo, const double *w, int m,
                      double *out, int64_t *n_uncovered);
 
+/* ---- ensemble sampler (sampler.py EnsembleSampler) ---------------------------------------------
+ * Goodman & Weare's affine-invariant stretch move in the red/blue half-ensemble form, resident on
+ * the device: the nwalkers walkers (double-double positions), their log-posteriors, the proposals,
+ * the priors, the accept test and the chain all stay there; per half-step the library enqueues
+ *   k_ens_propose -> k_point_tables -> pint_eval's launches (residual pass included) ->
+ *   k_point_lnl (or k_photon_lnl) -> k_ens_accept
+ * on the context's stream, with no host copy and no synchronisation between steps.  The random
+ * numbers are Philox4x32-10 blocks keyed by the seed and counted by (walker, step, half)
+ * (csrc/ensemble.hpp): a chain depends on the seed, the start and the step
+ * numbers only, and has the same bits on every run.
+ *
+ * pint_ens_init: the resident batch must be pint_set_points' with nwalkers / 2 points of one pulsar
+ * (the walkers of one half are its instances; their values are overwritten), nvar variables whose
+ * column in a walker's position is var_col[j].  kind PINT_ENS_WLS: the white-noise likelihood of
+ * pint_point_lnlike, narrowband or wideband; PINT_ENS_PHOTON: pint_point_photon_lnlike at one phase
+ * offset, the walker's column phase_col.  base_vals: nparams (hi, lo) pairs evaluated in place of a
+ * proposal whose prior is not finite (nothing invalid runs on its account; it is rejected).  prior:
+ * nparams rows of 6 doubles (kind, p0..p4: csrc/ensemble.hpp).  The class map tells which columns are
+ * the EFACs and EQUADs of every noise class: imap = ncls, ndmcls, nent, then ef_ptr[ncls + 1],
+ * eq_ptr[ncls + 1], dmef_ptr[ndmcls + 1], dmeq_ptr[ndmcls + 1] (ranges of entries) and ent_col[nent]
+ * (a column, or -1: the fixed value fmap[e]); Q^2 of a class is the sum of its EQUAD entries' squares,
+ * F the product of its EFAC entries, in entry order.  chunk: steps between two drains of the chain
+ * (0: chosen from the sizes).  step0: the number of the first step (the Philox counter continues a
+ * chain from there).  pos: nwalkers x nparams (hi, lo) pairs; their log-posteriors are evaluated
+ * through the same launches, and PINT_E_INVALID is returned if one is not finite.
+ * pint_ens_run: nsteps more steps; synchronises once per chunk, to drain the chain and to read the
+ * status word (flagged proposals -- Kepler, added delay -- are rejections counted per walker, not
+ * errors).  pint_ens_read: of the last pint_ens_run, chain_hi / chain_lo [nsteps][nwalkers][nparams]
+ * and lnprob [nsteps][nwalkers]; counters: accepted[nwalkers] then flagged[nwalkers] since
+ * pint_ens_init; state: the current positions hi[nwalkers][nparams], lo[...], then lnprob[nwalkers].
+ * Any pointer may be NULL.  pint_ens_close frees the sampler (so does pint_ctx_destroy). */
+#define PINT_ENS_WLS 0
+#define PINT_ENS_PHOTON 1
+int pint_ens_init(pint_ctx *ctx, int kind, int nwalkers, int nparams, int nvar, const int32_t *var_col,
+                  const double *base_vals, const double *prior, int phase_col, int nimap, const int32_t *imap,
+                  const double *fmap, uint64_t seed, double a, int chunk, int64_t step0, const double *pos);
+int pint_ens_run(pint_ctx *ctx, int64_t nsteps);
+int pint_ens_read(pint_ctx *ctx, double *chain_hi, double *chain_lo, double *lnprob, int32_t *counters, double *state);
+int pint_ens_close(pint_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,14 @@ def __getattr__(name):
     if name in ("Polycos", "PolycoEntry"):
         from . import polycos
         return getattr(polycos, name)
-    if name in ("eventstats", "event_optimize", "event_toas", "polycos"):
+    # the ensemble sampler over the batched posteriors, and the fitter on it
+    if name in ("EnsembleSampler", "get_initial_pos", "integrated_time"):
+        from . import sampler
+        return getattr(sampler, name)
+    if name == "MCMCFitter":
+        from .mcmc_fitter import MCMCFitter
+        return MCMCFitter
+    if name in ("eventstats", "event_optimize", "event_toas", "polycos", "sampler", "mcmc_fitter"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -39,6 +39,10 @@ MAX_POLYCO_COEFF = 16   # PINT_MAX_POLYCO_COEFF
 MAX_POLYCO_NODES = 64   # PINT_MAX_POLYCO_NODES
 PC_NF = 11              # PINT_PC_NF: header fields of a polyco entry (pint_set_polycos)
 
+ENS_WLS, ENS_PHOTON = 0, 1  # PINT_ENS_*: the sampler's target kinds
+ENS_PRIOR_FLAT, ENS_PRIOR_UNIFORM, ENS_PRIOR_NORMAL, ENS_PRIOR_PHASE, ENS_PRIOR_BNORMAL = range(5)  # csrc/ensemble.hpp
+ENS_PRIOR_W = 6
+
 PINT_OK, PINT_E_INVALID, PINT_E_HIP, PINT_E_NOT_PD, PINT_E_KEPLER, PINT_E_PARAM, PINT_E_SIGMA = range(7)
 
 dptr = C.POINTER(C.c_double)
@@ -225,6 +229,11 @@ def lib():
     L.pint_set_polycos.argtypes = [vp, C.c_int, C.c_int, dptr, dptr, dptr]
     L.pint_polyco_eval.argtypes = [vp, C.c_int64, dptr, dptr, C.c_int] + [dptr] * 4 + [i64p]
     L.pint_polyco_trig.argtypes = [vp, C.c_int64, dptr, dptr, dptr, C.c_int, dptr, i64p]
+    L.pint_ens_init.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), dptr, dptr, C.c_int, C.c_int,
+                                C.POINTER(C.c_int32), dptr, C.c_uint64, C.c_double, C.c_int, C.c_int64, dptr]
+    L.pint_ens_run.argtypes = [vp, C.c_int64]
+    L.pint_ens_read.argtypes = [vp, dptr, dptr, dptr, C.POINTER(C.c_int32), dptr]
+    L.pint_ens_close.argtypes = [vp]
     _lib = L
     L.pint_set_wideband.argtypes = [vp, C.c_int, dptr, dptr, dptr, C.POINTER(C.c_uint64)]
     L.pint_dm_resids.argtypes = [vp, C.c_int, C.c_int, dptr, dptr]
@@ -246,7 +255,8 @@ EXPORTED = ["pint_ctx_create", "pint_ctx_destroy", "pint_last_error", "pint_rele
             "pint_set_wavex", "pint_set_chromatic", "pint_set_fdjump", "pint_last_plan", "pint_set_phase_terms",
             "pint_set_points", "pint_set_dm_noise_classes", "pint_point_lnlike", "pint_point_lnlike_gls",
             "pint_set_photons", "pint_point_photon_lnlike", "pint_point_photon_trig",
-            "pint_polyco_fit", "pint_polyco_fit_host", "pint_set_polycos", "pint_polyco_eval", "pint_polyco_trig"]
+            "pint_polyco_fit", "pint_polyco_fit_host", "pint_set_polycos", "pint_polyco_eval", "pint_polyco_trig",
+            "pint_ens_init", "pint_ens_run", "pint_ens_read", "pint_ens_close"]
 
 
 def ptr(a: np.ndarray, ct=C.c_double):

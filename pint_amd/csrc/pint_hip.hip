@@ -28,6 +28,7 @@
 #include <functional>
 #include <chrono>
 #include "physics.hpp"
+#include "ensemble.hpp"
 
 using namespace pint;
 
@@ -6845,6 +6846,9 @@ struct pint_ctx {
     bool grid_valid = false;  // the batch is pint_set_grid's: grid_psr's points, options grid_opts
     std::vector<double> grid_spec_host;  // pint_set_grid's spec, kept while its upload may run
     int grid_psr = -1;
+    std::vector<int32_t> points_toff;  // the resident spec is pint_set_points': its variables' table offsets
+    bool points_valid = false;
+    struct EnsState* ens = nullptr;    // the ensemble sampler of this context (pint_ens_init)
     long grid_opts = 0;
     int small = 1;       // PINT_OPT_SMALL: k_gram_s / one-wave k_solve_blk for small instances
     int schur = 1;       // PINT_SCHUR: k_schur forms the DMX-eliminated solve's S', U, b'_d (deferred solves)
@@ -7597,6 +7601,7 @@ static void free_instances(pint_ctx* ctx) {
 void pint_ctx_destroy(pint_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
+    pint_ens_close(ctx);
     ctx->cq.clear();  // deferred reads never enqueued: their host buffers are not filled
     hipStreamSynchronize(ctx->stream);
     free_instances(ctx);
@@ -8269,6 +8274,7 @@ static int flush_chi2(pint_ctx* ctx);
 // The batch of pint_set_grid / pint_set_points: npts instances of pulsar psr, their tables still
 // to be formed by the caller's kernel.
 static int grid_batch(pint_ctx* ctx, int psr, int npts) {
+    ctx->points_valid = false;  // (pint_set_points marks its own spec afterwards)
     // the same pulsar and point count as the resident batch (the next grid over the same
     // TOAs, or the next chunk of one): every instance array, launch group and buffer is the
     // same, only the tables differ -- reset the batch's state as a fresh batch has it and
@@ -8370,6 +8376,19 @@ int pint_set_grid(pint_ctx* ctx, int psr, int npts, const double* base, int nvar
     return PINT_OK;
 }
 
+// The device half of pint_set_points: the batch's tables from the resident spec (base table, slot
+// map, the points' value pairs at d_gridspec + 2 ts -- staged by the host, or written there by
+// k_ens_propose).
+static int point_tables_launch(pint_ctx* ctx, int ts, int nvar, int npts) {
+    const long total = (long)npts * ts;
+    const int nb = (int)std::min<long>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(k_point_tables, dim3(nb), dim3(256), 0, ctx->stream, ctx->d_gridspec, ts, nvar, npts, ctx->d_tables);
+    HIPCHK(hipGetLastError());
+    ctx->spin_grid = 0;
+    ctx->tables_fresh = false;
+    return PINT_OK;
+}
+
 // npts points of one pulsar, each replacing any number of table entries (a sampler's walkers, a
 // nested sampler's live points): pint_set_grid's batch -- the same reuse of the resident one -- with
 // the tables formed by k_point_tables from the base table, a slot map and the points' values.
@@ -8390,6 +8409,8 @@ int pint_set_points(pint_ctx* ctx, int psr, int npts, const double* base, int nv
         map[o + 1] = 2.0 * j + 1.0;
     }
     if (int rc = grid_batch(ctx, psr, npts)) return rc;
+    ctx->points_toff.assign(var_toff, var_toff + nvar);
+    ctx->points_valid = true;
     // (the spec stays in the context until the next call, which synchronises the streams first)
     std::vector<double>& spec = ctx->grid_spec_host;
     const size_t nval = (size_t)2 * nvar * npts;
@@ -8402,12 +8423,7 @@ int pint_set_points(pint_ctx* ctx, int psr, int npts, const double* base, int nv
     dfree((void*&)ctx->d_gridspec);  // (the previous batch's: its tables were formed, the streams synchronised)
     HIPCHK(cmalloc((void**)&ctx->d_gridspec, sizeof(double) * spec.size()));
     HIPCHK(h2d(ctx->d_gridspec, spec.data(), sizeof(double) * spec.size(), ctx->stream, false));
-    const long total = (long)npts * ts;
-    const int nb = (int)std::min<long>((total + 255) / 256, 65536);
-    hipLaunchKernelGGL(k_point_tables, dim3(nb), dim3(256), 0, ctx->stream, ctx->d_gridspec, ts, nvar, npts, ctx->d_tables);
-    HIPCHK(hipGetLastError());
-    ctx->spin_grid = 0;
-    ctx->tables_fresh = false;
+    if (int rc = point_tables_launch(ctx, ts, nvar, npts)) return rc;
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }
@@ -8415,6 +8431,7 @@ int pint_set_points(pint_ctx* ctx, int psr, int npts, const double* base, int nv
 static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr, const double* tables) {
     if (!ctx || ninst <= 0) return PINT_E_INVALID;
     ctx->grid_valid = false;  // (pint_set_grid marks its own batch afterwards)
+    ctx->points_valid = false;
     ctx->tables_fresh = false;
     ctx->r2_pending = false;
     hipSetDevice(ctx->device);
@@ -10836,6 +10853,38 @@ int pint_set_dm_noise_classes(pint_ctx* ctx, int psr, int ncls, const int32_t* c
 // (bayesian.py:249 `.si.value`), a constant per DM row
 static const double PL_DM_LNUNIT = std::log(3.0856775814913673e22);
 
+// pint_point_lnlike's scratch (qf 2 nq | dqf 2 ndq | out 5 ni | qoff 2 ni, as doubles' storage), and
+// its device half: k_point_lnl on class values that are already resident (staged by the host, or
+// written by k_ens_propose).
+static int point_lnlike_scratch(pint_ctx* ctx, long nq, long ndq) {
+    const size_t need = (size_t)2 * nq + 2 * ndq + 5 * ctx->ninst + 2 * ctx->ninst;
+    if (need > ctx->pl_cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a lazy call's kernel may still read the old one)
+        if (ctx->d_pl) hipFree(ctx->d_pl);
+        ctx->d_pl = nullptr;
+        ctx->pl_cap = 0;
+        HIPCHK(hipMalloc(&ctx->d_pl, sizeof(double) * need));
+        ctx->pl_cap = need;
+    }
+    return PINT_OK;
+}
+static int point_lnlike_launch(pint_ctx* ctx, bool any_wb, const double* d_q, const double* d_dq, const long* qo,
+                               double* d_out) {
+    const int ni = ctx->ninst;
+    if (any_wb)
+        if (int rc = ensure_ic_solar_wind(ctx)) return rc;
+#define PINT_PL_ARGS ctx->d_psrs, ctx->d_inst, ni, ctx->d_tables, ctx->d_ic, ctx->d_rp, ctx->d_ftay, d_q, d_dq, qo, PL_DM_LNUNIT, d_out
+    if (ctx->maxn <= PL_SMALLN)
+        hipLaunchKernelGGL(k_point_lnl<1>, dim3((ni + 3) / 4), dim3(256), 0, ctx->stream, PINT_PL_ARGS);
+    else if (ctx->maxn <= PL_LARGEN)
+        hipLaunchKernelGGL(k_point_lnl<4>, dim3(ni), dim3(256), 0, ctx->stream, PINT_PL_ARGS);
+    else  // (8 waves, not 16: a 1024-thread workgroup's 128 VGPRs per lane made the DM rows spill)
+        hipLaunchKernelGGL(k_point_lnl<8>, dim3(ni), dim3(512), 0, ctx->stream, PINT_PL_ARGS);
+#undef PINT_PL_ARGS
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
 int pint_point_lnlike(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf, int64_t ndmcls_tot, const double* dmcls_qf,
                       double* out) {
     if (!ctx || ctx->ninst <= 0 || !cls_qf || !out) return PINT_E_INVALID;
@@ -10873,16 +10922,7 @@ int pint_point_lnlike(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf, int
     }
     flush_r2(ctx);
     hipSetDevice(ctx->device);
-    // scratch: qf 2 nq | dqf 2 ndq | out 5 ni | qoff 2 ni (as doubles' storage)
-    const size_t need = (size_t)2 * nq + 2 * ndq + 5 * ni + 2 * ni;
-    if (need > ctx->pl_cap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a lazy call's kernel may still read the old one)
-        if (ctx->d_pl) hipFree(ctx->d_pl);
-        ctx->d_pl = nullptr;
-        ctx->pl_cap = 0;
-        HIPCHK(hipMalloc(&ctx->d_pl, sizeof(double) * need));
-        ctx->pl_cap = need;
-    }
+    if (int rc = point_lnlike_scratch(ctx, nq, ndq)) return rc;
     double* d_q = ctx->d_pl;
     double* d_dq = d_q + 2 * nq;
     double* d_out = d_dq + 2 * ndq;
@@ -10891,18 +10931,7 @@ int pint_point_lnlike(pint_ctx* ctx, int64_t ncls_tot, const double* cls_qf, int
     HIPCHK(h2d(d_q, cls_qf, sizeof(double) * 2 * nq, ctx->stream, false));
     if (any_wb) HIPCHK(h2d(d_dq, dmcls_qf, sizeof(double) * 2 * ndq, ctx->stream, false));
     if (!one) HIPCHK(h2d(d_qoff, qoff.data(), sizeof(long) * qoff.size(), ctx->stream, true));
-    if (any_wb)
-        if (int rc = ensure_ic_solar_wind(ctx)) return rc;
-    const long* qo = one ? nullptr : d_qoff;
-#define PINT_PL_ARGS ctx->d_psrs, ctx->d_inst, ni, ctx->d_tables, ctx->d_ic, ctx->d_rp, ctx->d_ftay, d_q, d_dq, qo, PL_DM_LNUNIT, d_out
-    if (ctx->maxn <= PL_SMALLN)
-        hipLaunchKernelGGL(k_point_lnl<1>, dim3((ni + 3) / 4), dim3(256), 0, ctx->stream, PINT_PL_ARGS);
-    else if (ctx->maxn <= PL_LARGEN)
-        hipLaunchKernelGGL(k_point_lnl<4>, dim3(ni), dim3(256), 0, ctx->stream, PINT_PL_ARGS);
-    else  // (8 waves, not 16: a 1024-thread workgroup's 128 VGPRs per lane made the DM rows spill)
-        hipLaunchKernelGGL(k_point_lnl<8>, dim3(ni), dim3(512), 0, ctx->stream, PINT_PL_ARGS);
-#undef PINT_PL_ARGS
-    HIPCHK(hipGetLastError());
+    if (int rc = point_lnlike_launch(ctx, any_wb, d_q, d_dq, one ? nullptr : d_qoff, d_out)) return rc;
     HIPCHK(d2h(out, d_out, sizeof(double) * 5 * ni, ctx->stream));
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
@@ -11073,6 +11102,14 @@ static int photon_scratch(pint_ctx* ctx, size_t need) {
     return PINT_OK;
 }
 
+// pint_point_photon_lnlike's device half: k_photon_lnl on phase offsets that are already resident
+static int photon_lnl_launch(pint_ctx* ctx, int nphs, const double* d_phs, double* d_out) {
+    hipLaunchKernelGGL(k_photon_lnl, dim3(ctx->ninst, (nphs + PH_J - 1) / PH_J), dim3(PH_BT), 0, ctx->stream, ctx->d_inst,
+                       ctx->d_phot, ctx->d_phhi, ctx->d_phlo, nphs, d_phs, d_out);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
 int pint_point_photon_lnlike(pint_ctx* ctx, int nphs, const double* phs, double* out) {
     if (!ctx) return PINT_E_INVALID;
     if (ctx->ninst <= 0 || !ctx->phases_valid || !ctx->d_phhi || !phs || !out) {
@@ -11091,9 +11128,7 @@ int pint_point_photon_lnlike(pint_ctx* ctx, int nphs, const double* phs, double*
     double* d_phs = ctx->d_pp;
     double* d_out = d_phs + tot;
     HIPCHK(h2d(d_phs, phs, sizeof(double) * tot, ctx->stream, false));
-    hipLaunchKernelGGL(k_photon_lnl, dim3(ni, (nphs + PH_J - 1) / PH_J), dim3(PH_BT), 0, ctx->stream, ctx->d_inst,
-                       ctx->d_phot, ctx->d_phhi, ctx->d_phlo, nphs, d_phs, d_out);
-    HIPCHK(hipGetLastError());
+    if (int rc = photon_lnl_launch(ctx, nphs, d_phs, d_out)) return rc;
     HIPCHK(d2h(out, d_out, sizeof(double) * tot, ctx->stream));
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
@@ -11368,6 +11403,406 @@ int pint_polyco_trig(pint_ctx* ctx, int64_t n, const double* t_hi, const double*
     HIPCHK(hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *n_uncovered = (int64_t)cnt;
+    return PINT_OK;
+}
+
+}  // extern "C" (the sampler's kernels)
+
+// ---- ensemble sampler --------------------------------------------------------------------------
+// The arguments of the sampler's two kernels (by value).  Walker w of half s = w / h is instance
+// w - s h of the resident batch while its half moves.
+struct EnsK {
+    int W, d, h, kind, nvar, ncls, ndmcls, phase_col;
+    uint64_t seed;
+    double a;
+    double *xhi, *xlo, *lnp;                                        // the walkers [W][d], [W]
+    const double *prior, *base;                                     // [d][ENS_PRIOR_W]; base hi[d], lo[d]
+    const int *tcol, *ef_ptr, *eq_ptr, *dmef_ptr, *dmeq_ptr, *ent_col;  // the table variables' columns; the class map
+    const double* ent_val;
+    double *vals, *q, *dq, *phs;                                    // the existing passes' inputs
+    double *yhi, *ylo, *lpr, *zfac, *uacc;                          // the proposals of the moving half [h][d], [h]
+    int* mark;                                                      // [h]: the prior of the proposal is not finite
+    const double* lnl;                                              // the likelihood pass's output, lnl_stride per instance
+    int lnl_stride;
+    const int* istatus;
+    double *chain_hi, *chain_lo, *lnpc;                             // the chain chunk [chunk][W][d], [chunk][W]
+    int *nacc, *nflag;                                              // [W]
+};
+
+// One walker's value of class-map entry e as the likelihood pass takes it (a double)
+__device__ __forceinline__ double ens_entry(const EnsK& E, int i, bool bad, int e) {
+    const int c = E.ent_col[e];
+    return c < 0 ? E.ent_val[e] : (bad ? E.base[c] : E.yhi[(long)i * E.d + c]);
+}
+
+// k_ens_propose: one thread per walker of the moving half.  Draws (u_z, partner, u_acc), forms the
+// proposal in double-double and sums its log-prior; a proposal outside the prior is marked and the
+// base values take its place in what follows.  Writes what the existing passes read: the value
+// pairs of k_point_tables, the (Q^2, F) pairs of k_point_lnl's classes, the phase offset of
+// k_photon_lnl.  init: the walker itself is "proposed" (z = 1 exactly), to evaluate the start.
+__global__ __launch_bounds__(64) void k_ens_propose(EnsK E, int half, long step, int init) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= E.h) return;
+    const int w = half * E.h + i, d = E.d;
+    ens_draw dr;
+    dr.u_z = dr.u_acc = 0.5;
+    dr.idx = 0;
+    double z = 1.0;
+    if (!init) {
+        dr = ens_draws(E.seed, (uint32_t)w, (uint64_t)step, (uint32_t)half, E.h);
+        z = ens_stretch(E.a, dr.u_z);
+    }
+    const long xk = (long)w * d, xj = ((long)(1 - half) * E.h + dr.idx) * d, yo = (long)i * d;
+    double lp = 0.0;
+    for (int j = 0; j < d; j++) {
+        const dd k = dd_make(E.xhi[xk + j], E.xlo[xk + j]);
+        const dd y = init ? k : ens_propose(k, dd_make(E.xhi[xj + j], E.xlo[xj + j]), z);
+        E.yhi[yo + j] = y.hi;
+        E.ylo[yo + j] = y.lo;
+        lp = lp + ens_lnprior(E.prior + ENS_PRIOR_W * j, y.hi);
+    }
+    const bool bad = !(lp - lp == 0.0);  // (not finite)
+    E.mark[i] = bad ? 1 : 0;
+    E.lpr[i] = lp;
+    E.zfac[i] = (double)(d - 1) * log(z);
+    E.uacc[i] = dr.u_acc;
+    for (int v = 0; v < E.nvar; v++) {
+        const int c = E.tcol[v];
+        E.vals[2 * ((long)i * E.nvar + v)] = bad ? E.base[c] : E.yhi[yo + c];
+        E.vals[2 * ((long)i * E.nvar + v) + 1] = bad ? E.base[d + c] : E.ylo[yo + c];
+    }
+    if (E.kind == PINT_ENS_PHOTON) {
+        E.phs[i] = bad ? E.base[E.phase_col] : E.yhi[yo + E.phase_col];
+        return;
+    }
+    // (BayesianTiming._qf's order: Q^2 = 0 + v1^2 + ..., F = 1 v1 ...)
+    for (int c = 0; c < E.ncls; c++) {
+        double q2 = 0.0, f = 1.0;
+        for (int e = E.eq_ptr[c]; e < E.eq_ptr[c + 1]; e++) {
+            const double v = ens_entry(E, i, bad, e);
+            q2 = q2 + v * v;
+        }
+        for (int e = E.ef_ptr[c]; e < E.ef_ptr[c + 1]; e++) f = f * ens_entry(E, i, bad, e);
+        E.q[2 * ((long)i * E.ncls + c)] = q2;
+        E.q[2 * ((long)i * E.ncls + c) + 1] = f;
+    }
+    for (int c = 0; c < E.ndmcls; c++) {
+        double q2 = 0.0, f = 1.0;
+        for (int e = E.dmeq_ptr[c]; e < E.dmeq_ptr[c + 1]; e++) {
+            const double v = ens_entry(E, i, bad, e);
+            q2 = q2 + v * v;
+        }
+        for (int e = E.dmef_ptr[c]; e < E.dmef_ptr[c + 1]; e++) f = f * ens_entry(E, i, bad, e);
+        E.dq[2 * ((long)i * E.ndmcls + c)] = q2;
+        E.dq[2 * ((long)i * E.ndmcls + c) + 1] = f;
+    }
+}
+
+// k_ens_accept: one thread per walker of the moving half, after the likelihood pass.  lnq = prior +
+// likelihood; a marked proposal (prior not finite), a proposal the device flagged and a NaN are
+// rejected; else accepted iff log u_acc < (d - 1) log z + lnq - lnp.  Writes the walker's row of the
+// chain (row: the step's place in the chunk; < 0: none) and its counters with plain stores of its
+// own: the same bits on every run.  init: lnp = lnq, unconditionally.
+__global__ __launch_bounds__(64) void k_ens_accept(EnsK E, int half, int row, int init) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= E.h) return;
+    const int w = half * E.h + i, d = E.d;
+    const bool flagged = E.istatus[i] != 0;
+    double lnq = E.lpr[i] + E.lnl[(long)i * E.lnl_stride];
+    if (E.mark[i]) lnq = -INFINITY;
+    else if (flagged) lnq = NAN;
+    const bool nan = lnq != lnq;
+    if (init) {
+        E.lnp[w] = lnq;
+        return;
+    }
+    if (nan && !E.mark[i]) E.nflag[w] += 1;
+    const bool acc = !nan && !E.mark[i] && log(E.uacc[i]) < E.zfac[i] + lnq - E.lnp[w];
+    if (acc) {
+        for (int j = 0; j < d; j++) {
+            E.xhi[(long)w * d + j] = E.yhi[(long)i * d + j];
+            E.xlo[(long)w * d + j] = E.ylo[(long)i * d + j];
+        }
+        E.lnp[w] = lnq;
+        E.nacc[w] += 1;
+    }
+    if (row >= 0) {
+        const long o = ((long)row * E.W + w) * d;
+        for (int j = 0; j < d; j++) {
+            E.chain_hi[o + j] = E.xhi[(long)w * d + j];
+            E.chain_lo[o + j] = E.xlo[(long)w * d + j];
+        }
+        E.lnpc[(long)row * E.W + w] = E.lnp[w];
+    }
+}
+
+// The sampler of a context: the kernels' arguments, the device buffers behind them, and the host
+// copy of the last run's chain.
+struct EnsState {
+    EnsK k{};
+    int psr = -1, chunk = 0;
+    bool wb = false;
+    int64_t step = 0;                   // the number of the next step
+    std::vector<int32_t> var_toff;      // the batch's variables when the sampler was made
+    std::vector<void*> bufs;
+    std::vector<double> chain_hi, chain_lo, lnprob;
+    int64_t run_steps = 0;
+};
+
+extern "C" {
+
+int pint_ens_close(pint_ctx* ctx) {
+    if (!ctx) return PINT_E_INVALID;
+    if (!ctx->ens) return PINT_OK;
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    for (void* b : ctx->ens->bufs) hipFree(b);
+    delete ctx->ens;
+    ctx->ens = nullptr;
+    return PINT_OK;
+}
+
+// the resident batch is still the one the sampler was made on (pint_set_points, the walkers of a half)
+static int ens_batch_ok(pint_ctx* ctx, const EnsState* S, const char* who) {
+    if (!ctx->grid_valid || !ctx->points_valid || ctx->grid_psr != S->psr || ctx->ninst != S->k.h ||
+        ctx->points_toff != S->var_toff || !ctx->d_gridspec || ctx->upsr.size() != 1) {
+        ctx->err = std::string(who) + ": the resident batch is not pint_set_points' batch of nwalkers / 2 points with the "
+                                      "sampler's variables (install it again before the call)";
+        return PINT_E_INVALID;
+    }
+    return PINT_OK;
+}
+
+// One half-step (init: the evaluation of the start): propose, tables, evaluation with the residual
+// pass, likelihood, accept -- enqueued in that order on the context's stream, which orders them.
+static int ens_half(pint_ctx* ctx, EnsState* S, int half, int64_t step, int row, int init) {
+    const EnsK& K = S->k;
+    const int nb = (K.h + 63) / 64;
+    hipLaunchKernelGGL(k_ens_propose, dim3(nb), dim3(64), 0, ctx->stream, K, half, (long)step, init);
+    HIPCHK(hipGetLastError());
+    if (int rc = point_tables_launch(ctx, ctx->psrs[S->psr].spec.tstride, K.nvar, K.h)) return rc;
+    HIPCHK(hipMemsetAsync(ctx->d_istatus, 0, sizeof(int) * K.h, ctx->stream));
+    ctx->ic_valid = false;  // (new tables: the evaluation forms the instances' constants again)
+    ctx->restore_pending = false;
+    if (int rc = pint_eval(ctx, 0)) return rc;
+    if (K.kind == PINT_ENS_PHOTON) {
+        if (int rc = photon_lnl_launch(ctx, 1, K.phs, const_cast<double*>(K.lnl))) return rc;
+    } else {
+        flush_r2(ctx);
+        if (int rc = point_lnlike_launch(ctx, S->wb, K.q, K.dq, nullptr, const_cast<double*>(K.lnl))) return rc;
+    }
+    hipLaunchKernelGGL(k_ens_accept, dim3(nb), dim3(64), 0, ctx->stream, K, half, row, init);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+// The passes' scratch of this batch, and the kernels' pointers into it (and into the resident spec)
+static int ens_bind(pint_ctx* ctx, EnsState* S, const char* who) {
+    if (int rc = ens_batch_ok(ctx, S, who)) return rc;
+    EnsK& K = S->k;
+    const int ts = ctx->psrs[S->psr].spec.tstride;
+    K.vals = ctx->d_gridspec + 2 * (size_t)ts;
+    K.istatus = ctx->d_istatus;
+    if (K.kind == PINT_ENS_PHOTON) {
+        if (int rc = photon_ready(ctx, who, true)) return rc;
+        if (int rc = photon_scratch(ctx, 2 * (size_t)K.h)) return rc;
+        K.phs = ctx->d_pp;
+        K.lnl = ctx->d_pp + K.h;
+        K.lnl_stride = 1;
+    } else {
+        const long nq = (long)K.h * K.ncls, ndq = (long)K.h * K.ndmcls;
+        if (int rc = point_lnlike_scratch(ctx, nq, ndq)) return rc;
+        K.q = ctx->d_pl;
+        K.dq = K.q + 2 * nq;
+        K.lnl = K.dq + 2 * ndq;
+        K.lnl_stride = 5;
+    }
+    return PINT_OK;
+}
+
+// the status word after a chunk: flagged proposals were rejected per walker; anything else is an error
+static int ens_status(pint_ctx* ctx) {
+    int st = 0;
+    HIPCHK(hipMemcpyAsync(&st, ctx->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (st) HIPCHK(hipMemsetAsync(ctx->d_status, 0, sizeof(int), ctx->stream));
+    return decode_status(ctx, st & ~((1 << PINT_E_KEPLER) | (1 << PINT_E_PARAM)));
+}
+
+int pint_ens_init(pint_ctx* ctx, int kind, int nwalkers, int nparams, int nvar, const int32_t* var_col,
+                  const double* base_vals, const double* prior, int phase_col, int nimap, const int32_t* imap,
+                  const double* fmap, uint64_t seed, double a, int chunk, int64_t step0, const double* pos) {
+    if (!ctx) return PINT_E_INVALID;
+    auto bad = [&](const std::string& m) { ctx->err = "pint_ens_init: " + m; return PINT_E_INVALID; };
+    if (kind != PINT_ENS_WLS && kind != PINT_ENS_PHOTON) return bad("unknown target kind");
+    if (nwalkers < 4 || nwalkers % 2) return bad("the number of walkers must be even and at least 4");
+    if (nparams < 1 || nvar < 0 || nvar > nparams || (nvar && !var_col) || !base_vals || !prior || !pos || !imap ||
+        nimap < 3 || chunk < 0 || step0 < 0)
+        return bad("bad argument");
+    if (!(a > 1.0)) return bad("the stretch scale a must be > 1");
+    const int h = nwalkers / 2, d = nparams;
+    if (!ctx->grid_valid || !ctx->points_valid || ctx->ninst != h || (int)ctx->points_toff.size() != nvar ||
+        ctx->upsr.size() != 1)
+        return bad("the resident batch must be pint_set_points' with nwalkers / 2 points and nvar variables");
+    const int psr = ctx->grid_psr;
+    const PsrDev& pd = ctx->psrs[psr].dev;
+    for (int j = 0; j < nvar; j++)
+        if (var_col[j] < 0 || var_col[j] >= d) return bad("a variable's column is outside the position");
+    for (int j = 0; j < d; j++) {
+        const double kd = prior[ENS_PRIOR_W * j];
+        if (!(kd == ENS_PRIOR_FLAT || kd == ENS_PRIOR_UNIFORM || kd == ENS_PRIOR_NORMAL || kd == ENS_PRIOR_PHASE ||
+              kd == ENS_PRIOR_BNORMAL))
+            return bad("unknown prior kind of parameter " + std::to_string(j));
+    }
+    const int ncls = imap[0], ndmcls = imap[1], nent = imap[2];
+    if (ncls < 0 || ndmcls < 0 || nent < 0 || nimap != 3 + 2 * (ncls + 1) + 2 * (ndmcls + 1) + nent || (nent && !fmap))
+        return bad("bad class map");
+    if (kind == PINT_ENS_WLS) {
+        if (pd.ncls <= 0 || ncls != pd.ncls) return bad("the class map does not have the pulsar's noise classes");
+        if (pd.wb ? (pd.ndmcls <= 0 || ndmcls != pd.ndmcls) : ndmcls != 0)
+            return bad("the class map does not have the pulsar's DM noise classes");
+    } else {
+        if (ncls || ndmcls) return bad("a photon target has no noise classes");
+        if (phase_col < 0 || phase_col >= d) return bad("a photon target needs the column of PHASE");
+    }
+    {
+        const int32_t* p = imap + 3;
+        const int cnt[4] = {ncls, ncls, ndmcls, ndmcls};
+        for (int g = 0; g < 4; g++) {
+            for (int c = 0; c <= cnt[g]; c++)
+                if (p[c] < 0 || p[c] > nent || (c && p[c] < p[c - 1])) return bad("bad class map range");
+            p += cnt[g] + 1;
+        }
+        for (int e = 0; e < nent; e++)
+            if (p[e] < -1 || p[e] >= d) return bad("a class map column is outside the position");
+    }
+    hipSetDevice(ctx->device);
+    pint_ens_close(ctx);
+    EnsState* S = new EnsState;
+    ctx->ens = S;  // (a failure below leaves it to pint_ens_close)
+    S->psr = psr;
+    S->wb = pd.wb != 0;
+    S->var_toff = ctx->points_toff;
+    S->step = step0;
+    EnsK& K = S->k;
+    K.W = nwalkers; K.d = d; K.h = h; K.kind = kind; K.nvar = nvar; K.ncls = ncls; K.ndmcls = ndmcls;
+    K.phase_col = phase_col; K.seed = seed; K.a = a;
+    if (!chunk) {  // at most ~64 MiB of chain on the device, 1..1024 steps
+        const size_t per = (size_t)nwalkers * (16 * (size_t)d + 8);
+        chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)64 << 20) / per));
+    }
+    S->chunk = chunk;
+    auto dalloc = [&](size_t bytes, const void* src) -> void* {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+        S->bufs.push_back(p);
+        if (src ? h2d(p, src, bytes, nullptr, true) != hipSuccess : hipMemset(p, 0, std::max<size_t>(bytes, 8)) != hipSuccess)
+            return nullptr;
+        return p;
+    };
+    const size_t Wd = (size_t)nwalkers * d, hd = (size_t)h * d;
+    std::vector<double> x(2 * Wd), bs(2 * (size_t)d);
+    for (size_t e = 0; e < Wd; e++) { x[e] = pos[2 * e]; x[Wd + e] = pos[2 * e + 1]; }
+    for (int j = 0; j < d; j++) { bs[j] = base_vals[2 * j]; bs[d + j] = base_vals[2 * j + 1]; }
+    std::vector<int32_t> im(imap + 3, imap + nimap);
+    im.insert(im.end(), var_col, var_col + nvar);
+    double* dx = (double*)dalloc(sizeof(double) * (2 * Wd + nwalkers), nullptr);
+    double* dpr = (double*)dalloc(sizeof(double) * ENS_PRIOR_W * d, prior);
+    double* dbs = (double*)dalloc(sizeof(double) * 2 * d, bs.data());
+    int* dim_ = (int*)dalloc(sizeof(int32_t) * im.size(), im.data());
+    double* dfm = (double*)dalloc(sizeof(double) * std::max(nent, 1), nent ? fmap : nullptr);
+    double* dy = (double*)dalloc(sizeof(double) * (2 * hd + 3 * (size_t)h), nullptr);
+    int* dmk = (int*)dalloc(sizeof(int) * ((size_t)h + 2 * (size_t)nwalkers), nullptr);
+    double* dch = (double*)dalloc(sizeof(double) * (size_t)chunk * (2 * Wd + nwalkers), nullptr);
+    if (!dx || !dpr || !dbs || !dim_ || !dfm || !dy || !dmk || !dch ||
+        h2d(dx, x.data(), sizeof(double) * 2 * Wd, nullptr, true) != hipSuccess) {
+        pint_ens_close(ctx);
+        ctx->err = "pint_ens_init: device allocation or upload failed";
+        return PINT_E_HIP;
+    }
+    K.xhi = dx; K.xlo = dx + Wd; K.lnp = dx + 2 * Wd;
+    K.prior = dpr; K.base = dbs;
+    K.ef_ptr = dim_; K.eq_ptr = K.ef_ptr + ncls + 1; K.dmef_ptr = K.eq_ptr + ncls + 1; K.dmeq_ptr = K.dmef_ptr + ndmcls + 1;
+    K.ent_col = K.dmeq_ptr + ndmcls + 1; K.tcol = K.ent_col + nent;
+    K.ent_val = dfm;
+    K.yhi = dy; K.ylo = dy + hd; K.lpr = dy + 2 * hd; K.zfac = K.lpr + h; K.uacc = K.zfac + h;
+    K.mark = dmk; K.nacc = dmk + h; K.nflag = K.nacc + nwalkers;
+    K.chain_hi = dch; K.chain_lo = dch + (size_t)chunk * Wd; K.lnpc = dch + 2 * (size_t)chunk * Wd;
+    // the start's log-posteriors through the same launches
+    int rc = ens_bind(ctx, S, "pint_ens_init");
+    const int lazy = ctx->lazy;
+    ctx->lazy = 1;
+    for (int half = 0; half < 2 && !rc; half++) rc = ens_half(ctx, S, half, 0, -1, 1);
+    ctx->lazy = lazy;
+    if (!rc) rc = ens_status(ctx);
+    std::vector<double> lnp(nwalkers);
+    if (!rc && hipMemcpy(lnp.data(), K.lnp, sizeof(double) * nwalkers, hipMemcpyDeviceToHost) != hipSuccess) {
+        ctx->err = "pint_ens_init: reading the initial log-posteriors failed";
+        rc = PINT_E_HIP;
+    }
+    if (!rc)
+        for (int w = 0; w < nwalkers; w++)
+            if (!(lnp[w] - lnp[w] == 0.0)) {
+                ctx->err = "pint_ens_init: the initial position of walker " + std::to_string(w) +
+                           " has no finite log-posterior (outside the prior, or the model cannot be evaluated there)";
+                rc = PINT_E_INVALID;
+                break;
+            }
+    if (rc) {
+        const std::string msg = ctx->err;
+        pint_ens_close(ctx);
+        ctx->err = msg;
+    }
+    return rc;
+}
+
+int pint_ens_run(pint_ctx* ctx, int64_t nsteps) {
+    if (!ctx) return PINT_E_INVALID;
+    EnsState* S = ctx->ens;
+    if (!S || nsteps < 0) { ctx->err = "pint_ens_run: no sampler (pint_ens_init), or a negative step count"; return PINT_E_INVALID; }
+    hipSetDevice(ctx->device);
+    if (int rc = ens_bind(ctx, S, "pint_ens_run")) return rc;
+    const EnsK& K = S->k;
+    const size_t Wd = (size_t)K.W * K.d;
+    S->chain_hi.resize((size_t)nsteps * Wd);
+    S->chain_lo.resize((size_t)nsteps * Wd);
+    S->lnprob.resize((size_t)nsteps * K.W);
+    S->run_steps = 0;
+    const int lazy = ctx->lazy;
+    int rc = PINT_OK;
+    for (int64_t t0 = 0; t0 < nsteps && !rc; t0 += S->chunk) {
+        const int nc = (int)std::min<int64_t>(S->chunk, nsteps - t0);
+        ctx->lazy = 1;  // (the evaluation only enqueues)
+        for (int r = 0; r < nc && !rc; r++)
+            for (int half = 0; half < 2 && !rc; half++) rc = ens_half(ctx, S, half, S->step + r, r, 0);
+        ctx->lazy = lazy;
+        if (rc) break;
+        // the one synchronisation of the chunk: its chain and the status word
+        HIPCHK(d2h(S->chain_hi.data() + (size_t)t0 * Wd, K.chain_hi, sizeof(double) * nc * Wd, ctx->stream));
+        HIPCHK(d2h(S->chain_lo.data() + (size_t)t0 * Wd, K.chain_lo, sizeof(double) * nc * Wd, ctx->stream));
+        HIPCHK(d2h(S->lnprob.data() + (size_t)t0 * K.W, K.lnpc, sizeof(double) * nc * K.W, ctx->stream));
+        rc = ens_status(ctx);
+        if (!rc) {
+            S->step += nc;
+            S->run_steps += nc;
+        }
+    }
+    return rc;
+}
+
+int pint_ens_read(pint_ctx* ctx, double* chain_hi, double* chain_lo, double* lnprob, int32_t* counters, double* state) {
+    if (!ctx) return PINT_E_INVALID;
+    EnsState* S = ctx->ens;
+    if (!S) { ctx->err = "pint_ens_read: no sampler (pint_ens_init)"; return PINT_E_INVALID; }
+    const EnsK& K = S->k;
+    const size_t Wd = (size_t)K.W * K.d, n = (size_t)S->run_steps;
+    if (chain_hi && n) memcpy(chain_hi, S->chain_hi.data(), sizeof(double) * n * Wd);
+    if (chain_lo && n) memcpy(chain_lo, S->chain_lo.data(), sizeof(double) * n * Wd);
+    if (lnprob && n) memcpy(lnprob, S->lnprob.data(), sizeof(double) * n * K.W);
+    hipSetDevice(ctx->device);
+    if (counters) HIPCHK(hipMemcpyAsync(counters, K.nacc, sizeof(int32_t) * 2 * K.W, hipMemcpyDeviceToHost, ctx->stream));
+    if (state) HIPCHK(hipMemcpyAsync(state, K.xhi, sizeof(double) * (2 * Wd + K.W), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
 }
 

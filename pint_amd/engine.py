@@ -883,6 +883,8 @@ class Session:
         pairs = np.empty((npts, len(names), 2))
         pairs[:, :, 0] = v  # (a longdouble rounds to its nearest double: split_ld's hi)
         pairs[:, :, 1] = (v - pairs[:, :, 0].astype(v.dtype)) if v.dtype == np.longdouble else 0.0
+        if getattr(values, "pairs", None) is not None:  # (pointbatch.PairPoints: the pairs as they were given)
+            pairs[:] = values.pairs
         toff = np.array([lay.offsets[p] for p in names], dtype=np.int32)
         self._check(self.L.pint_set_points(self.ctx, lay.psr_id, int(npts), L.ptr(base), len(names),
                                            L.ptr(toff, C.c_int32), L.ptr(pairs)))

@@ -25,6 +25,49 @@ def _is_unbounded(prior) -> bool:
     return isinstance(rv, UniformUnboundedRV) or isinstance(getattr(rv, "dist", None), UniformUnboundedRV)
 
 
+class PairPoints(np.ndarray):
+    """Points given as (hi, lo) pairs of doubles: a longdouble array (hi + lo rounded to its 64 bits)
+    that keeps the pairs themselves in ``pairs`` (float64, the array's shape + (2,)).  A double-double
+    value -- an ensemble sampler's walker -- carries ~106 bits, and the device table takes both halves:
+    Session.set_points hands on the pairs as they are.  Everything else (priors, noise parameters)
+    reads the rounded value.  Indexing and copies keep the pairs in step; assignment writes the
+    assigned values' own pairs."""
+
+    def __new__(cls, pairs):
+        pairs = np.array(pairs, dtype=np.float64)
+        v = np.atleast_1d(pairs[..., 0].astype(LD) + pairs[..., 1].astype(LD))
+        # a reader that rounds to double must get hi, the pair's own rounding: where the sum's 64 bits
+        # end on a tie that would round away from it, the neighbour towards hi (one longdouble ulp)
+        off = v.astype(np.float64) != pairs[..., 0]
+        if np.any(off):
+            v[off] = np.nextafter(v[off], pairs[..., 0][off].astype(LD))
+        obj = np.ascontiguousarray(v.reshape(pairs.shape[:-1])).view(cls)
+        obj.pairs = pairs
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.pairs = None
+
+    def __getitem__(self, idx):
+        r = super().__getitem__(idx)
+        if isinstance(r, PairPoints) and self.pairs is not None:
+            r.pairs = self.pairs[idx]
+        return r
+
+    def __setitem__(self, idx, value):
+        super().__setitem__(idx, value)
+        if self.pairs is not None:
+            v = np.asarray(value, dtype=LD)
+            hi = v.astype(np.float64)
+            self.pairs[idx] = getattr(value, "pairs", None) if getattr(value, "pairs", None) is not None else \
+                np.stack([hi, (v - hi.astype(LD)).astype(np.float64)], axis=-1)
+
+    def copy(self, order="C"):
+        r = super().copy(order)
+        r.pairs = None if self.pairs is None else self.pairs.copy()
+        return r
+
+
 class PointBatch:
     # -- construction ------------------------------------------------------------------
     def _apply_prior_info(self, prior_info):
@@ -58,7 +101,12 @@ class PointBatch:
 
     # -- arguments ---------------------------------------------------------------------
     def _points(self, params, batch):
-        v = np.asarray(params)
+        if isinstance(params, PairPoints):
+            v = params
+        elif batch and isinstance(params, np.ndarray) and params.ndim == 3 and params.shape[1:] == (self.nparams, 2):
+            v = PairPoints(params)  # (N, nparams, 2): (hi, lo) pairs
+        else:
+            v = np.asarray(params)
         if v.dtype != LD:
             v = v.astype(np.float64)
         if not batch:
