@@ -6810,6 +6810,7 @@ enum : unsigned {
 
 struct pint_ctx {
     int device = 0;
+    int ncu = 256;  // the device's compute units (pint_ctx_create; plan_batch sizes the Gram launches by them)
     hipStream_t stream = nullptr;
     hipStream_t cstream = nullptr;   // copy stream: fit outputs -> host, overlapped with compute
     hipEvent_t ev_solved = nullptr, ev_copied = nullptr;
@@ -6886,7 +6887,7 @@ struct pint_ctx {
     double* d_rpart = nullptr;    // per residual block: sum w, sum w x, chi2 partial
     double* d_epart = nullptr;    // fused residual pass (efz): per evaluation block sum w, sum w x
     int efz = 0;                  // the batch's evaluation blocks carry k_resid1 (EF_ROWS rows + row 0 + TZR)
-    unsigned post = 0;  // POST_*: the passes that follow the batch's evaluation (set_instances_impl)
+    unsigned post = 0;  // POST_*: the passes that follow the batch's evaluation (plan_batch)
     int efuse = 1;                // PINT_EFUSE: fuse k_resid1 into the evaluation of large instances
     int lane_solve = 1;           // PINT_LANE_SOLVE: k_solve_lanes for small-instance batches of K <= 8
     std::vector<int> upsr;        // the batch's distinct pulsars (host plans loop over these, not instances)
@@ -7494,6 +7495,10 @@ pint_ctx* pint_ctx_create(int device) {
         ctx->err = "hipSetDevice failed";
         return ctx;
     }
+    {
+        int ncu = 0;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) ctx->ncu = ncu;
+    }
     // (stream priorities -- the kernel stream highest, the copy stream lowest -- measured no
     // different in round 4: 0.376-0.384 vs 0.380-0.387 ms per 68-pulsar step)
     ctx->stream = stream_get(device, STREAM_KERNEL);
@@ -7545,6 +7550,533 @@ pint_ctx* pint_ctx_create(int device) {
 
 const char* pint_last_error(pint_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
+// ---------------------------------------------------------------------------------
+// The layout of a batch: everything pint_set_instances decides, as a value.  plan_batch forms
+// it from the context's pulsars by host arithmetic alone (no HIP call, nothing written to the
+// context or its pulsars); commit_batch carries it out.  A new layout decision is a field
+// here, chosen in one planner step and read by the commit or by a launch.
+struct GramOrder {  // one of k_gram's three launch orders (full, compact, compact on k_gram_v)
+    std::vector<KpGroup> groups;
+    std::vector<int> order;  // the instances in launch order
+    bool ident;              // ... which is the batch's own order of all its instances: d_inst serves
+};
+struct VgChoice {  // a pulsar's k_gram_v layout in this batch (PsrDev's fields of the same names)
+    int vg, vb, vns, vkp;
+    bool reslot;   // its rows' slot ids are formed again: vns differs from PsrHost::dslot_ns
+};
+struct BatchLayout {
+    const char* err;  // set: the batch is refused and nothing else here is meaningful
+    unsigned post;    // POST_*
+    int efz, nsplit;
+    int force_ntr;    // the row-tile count every k_gram_v pulsar takes at least (0: its own)
+    std::vector<VgChoice> vg;   // per pulsar of the context, in the batch or not
+    std::vector<InstDev> inst;  // (spec and runs, device pointers, are the commit's to fill)
+    long tot_table, tot_rows, tot_m, tot_g, tot_s, tot_c, tot_out, tot_cv, tot_e, tot_ep, tot_sd, tot_dd;
+    long vgoff, vboff, xwoff;  // doubles of d_Sdp, d_BFp and each d_xw_s
+    int maxK, maxn, max_ts, max_nep, max_ndc, n_vg, vb_on;
+    bool any_dmx_rows;
+    bool sw, any_dmn;       // a pulsar with NE_SW (d_swg), with PLDMNoise (d_dfac)
+    std::vector<int> upsr;  // the batch's distinct pulsars, in order of first use
+    std::vector<int> blk_inst, blk_row0;  // evaluation blocks, by block kind
+    int blk_off[PINT_NBLK + 1], nblk;
+    std::vector<int> rblk_inst;  // residual blocks (as many trig tiles with wfuse)
+    long ebn;                    // evaluation blocks carrying the fused residual pass
+    GramOrder order[3];
+    bool wfuse;
+    int wstride;
+};
+
+// Pulsar ids within the context and binary models the evaluation has a block kind for.
+static const char* batch_refusal(const pint_ctx* ctx, int ninst, const int32_t* inst_psr) {
+    for (int k = 0; k < ninst; k++) {
+        const int p = inst_psr[k];
+        if (p < 0 || p >= (int)ctx->psrs.size()) return "bad pulsar id";
+    }
+    for (int k = 0; k < ninst; k++) {
+        const int bt = ctx->psrs[inst_psr[k]].spec.binary;
+        if (bt < 0 || bt >= PINT_NBIN) return "bad binary model";
+    }
+    return nullptr;
+}
+
+// The passes after the evaluation that some instance of the batch needs.
+static unsigned batch_post(const pint_ctx* ctx, int ninst, const int32_t* inst_psr) {
+    unsigned post = 0;
+    for (int k = 0; k < ninst; k++) {
+        const PsrHost& e = ctx->psrs[inst_psr[k]];
+        const PsrDev& d = e.dev;
+        if (d.nwx + d.ndmwx > 0) post |= POST_WAVEX;
+        if (d.ncm + d.ncmwx > 0) post |= POST_WAVEX | POST_CHROM;  // (the same pass, in its chromatic build)
+        if (d.nfdj + d.nfdjdm > 0) post |= POST_FDJUMP;
+        if (e.spec.nglitch > 0) post |= POST_GLITCH;
+        if (d.npw + d.nwave + d.nifunc > 0) post |= POST_PHASE_TERMS;
+    }
+    return post;
+}
+
+// Two predicates say "this pulsar would take k_gram_v", and they DIFFER: vg_counted, which
+// gram_slots uses to pick the resident workgroups per CU for the N-split, does not ask that the
+// red-noise basis be generated (no PLDMNoise: dmn0 >= nred); vg_ok, which decides the layout
+// (choose_force_ntr, plan_vgram), does.  A PLDMNoise pulsar so counts toward the "majority on
+// k_gram_v" although it never takes that path.  Making them one changes nsplit for such batches.
+static bool vg_counted(const pint_ctx* ctx, const PsrHost& ph) {
+    const PsrDev& d = ph.dev;
+    return ctx->vgram && d.dsplit && d.dcontig && d.nep == 0 && ph.spec.nred <= VTRIG / 2 - 1 && d.red0c + 1 <= VMAXR0;
+}
+// vg compact path (k_gram_v): contiguous DMX bins, no ECORR, nred <= 31, <= 47 timing columns
+static bool vg_ok(const pint_ctx* ctx, const PsrHost& ph) {
+    return vg_counted(ctx, ph) && ph.spec.dmn0 >= ph.spec.nred;  // PLDMNoise: stored, per-TOA scaled basis
+}
+
+// Resident Gram workgroups of the chip: k_gram runs one per CU, k_gram_v GWG; the batch's
+// majority path decides
+static long gram_slots(const pint_ctx* ctx, int ninst, const int32_t* inst_psr, int ncu) {
+    long nvgc = 0;
+    for (int k = 0; k < ninst; k++) nvgc += vg_counted(ctx, ctx->psrs[inst_psr[k]]) ? 1 : 0;
+    return (long)ncu * (2 * nvgc > ninst ? GWG : 1);
+}
+
+// N-split for the Gram so the launch fills the CUs: the split count that minimises
+// (workgroup rounds) / nsplit, i.e. the k_gram makespan with `slots` workgroups resident, with
+// >= 4 chunks per split
+static int choose_nsplit(int ninst, int maxN, long slots) {
+    int maxsplit = (maxN + 4 * GCH - 1) / (4 * GCH);
+    if (maxsplit < 1) maxsplit = 1;
+    // A batch too small to fill the chip even at the finest split (a single fit, a few
+    // pulsars) is latency-bound: splits of 128 rows leave each workgroup two chunks while
+    // k_greduce sums hundreds of partials per Gram element.  Keep >= 512 rows per split there.
+    if ((long)ninst * maxsplit < slots) maxsplit = std::max(1, std::min(maxsplit, (maxN + 511) / 512));
+    // (smallest split count within 3% of the best makespan: each split adds a partial
+    // Gram that k_greduce must sum)
+    auto cost = [&](int ns) { return (double)(((long)ninst * ns + slots - 1) / slots) / ns; };
+    double best = 1e30;
+    for (int ns = 1; ns <= maxsplit && ns <= 4096; ns++) best = std::min(best, cost(ns));
+    int nsplit = 1;
+    for (int ns = 1; ns <= maxsplit && ns <= 4096; ns++)
+        if (cost(ns) <= best * 1.03) { nsplit = ns; break; }
+    // (measured on the 68-pulsar PTA, round 4: 7 splits -- one round of workgroups, many CUs
+    // with one -- 0.120 ms of k_gram_v, 8: 0.147, 11: 0.104, this model's 15: 0.089-0.093)
+    if (const char* e = getenv("PINT_NSPLIT")) {  // (diagnostic sweeps: a fixed split count)
+        const int v = atoi(e);
+        if (v >= 1) nsplit = std::min(v, std::max(1, (maxN + 63) / 64));
+    }
+    return nsplit;
+}
+
+// k_gram_v with ntr row tiles: the DMX slots fill the [T | r] row tiles such that the bins of
+// every N-split are distinct mod the slot count; LDS width <= VMAXKP
+static bool slots_ok(const PsrHost& ph, int ntr, int nsplit) {
+    const PsrDev& d = ph.dev;
+    const int wt = d.red0c + 1, R = d.Kd - d.red0c;
+    const int ns = 16 * ntr - wt, kpv = (16 * ntr + R + 15) / 16 * 16;
+    if (ns < 1 || kpv > VMAXKP) return false;
+    long per = (ph.n + nsplit - 1) / nsplit;
+    per = (per + 3) / 4 * 4;
+    for (int sp = 0; sp < nsplit; sp++) {
+        const long i0 = sp * per, i1 = std::min<long>(i0 + per, ph.n);
+        std::vector<char> seen(ns, 0);
+        for (int a = 0; a < d.ndc; a++) {
+            if (ph.dhi[a] <= ph.dlo[a] || ph.dlo[a] >= i1 || ph.dhi[a] <= i0) continue;
+            if (seen[a % ns]) return false;
+            seen[a % ns] = 1;
+        }
+    }
+    return true;
+}
+// the fewest row tiles >= ntr0 (and at most two beyond the [T | r] columns' own, 3 in all)
+// that pass slots_ok; 0: none
+static int first_ntr(const PsrHost& ph, int ntr0, int nsplit) {
+    const int wt = ph.dev.red0c + 1;
+    for (int ntr = ntr0; ntr <= std::min(3, (wt + 15) / 16 + 2); ntr++)
+        if (slots_ok(ph, ntr, nsplit)) return ntr;
+    return 0;
+}
+
+// A batch whose Gram workgroups fit one resident round (a few pulsars: the per-rank shard
+// of a PTA over several GPUs) is latency-bound, and every distinct k_gram_v tile shape is
+// a launch of its own, in sequence: there all vg pulsars take the largest row-tile count
+// any of them needs (more padding MFMAs, one launch)
+static int choose_force_ntr(const pint_ctx* ctx, int ninst, const int32_t* inst_psr, int nsplit, long slots) {
+    if ((long)ninst * nsplit > slots) return 0;
+    int force_ntr = 0;
+    std::vector<char> inb(ctx->psrs.size(), 0);
+    for (int k = 0; k < ninst; k++) inb[inst_psr[k]] = 1;
+    for (size_t p = 0; p < ctx->psrs.size(); p++) {
+        const PsrHost& ph = ctx->psrs[p];
+        if (!inb[p] || !vg_ok(ctx, ph)) continue;
+        force_ntr = std::max(force_ntr, first_ntr(ph, (ph.dev.red0c + 1 + 15) / 16, nsplit));
+    }
+    return force_ntr;
+}
+
+// VB (binned DMX x F): the 16 rows a wave takes from one chunk (split sp, quarter w,
+// rows i0 + w QV + 16 c ..) hold at most two bins, of distinct parity (drow)
+static bool vb_rows_ok(const PsrHost& ph, int nsplit) {
+    long per = (ph.n + nsplit - 1) / nsplit;
+    per = (per + 3) / 4 * 4;
+    const std::vector<int>& dr = ph.drow_host;
+    for (int sp = 0; sp < nsplit; sp++) {
+        const long i0 = std::min<long>((long)sp * per, ph.n), i1 = std::min<long>(i0 + per, ph.n);
+        const long QV = (i1 - i0 + VCH - 1) / VCH * 16;
+        for (long g = 0; g < i1 - i0; g += 16) {  // g = w QV + 16 c
+            const long gend = std::min<long>(g + 16, (g / QV + 1) * QV);
+            int b0 = -1, b1 = -1;
+            for (long r = g; r < gend && r < i1 - i0; r++) {
+                const int b = dr[i0 + r];
+                if (b < 0 || b == b0 || b == b1) continue;
+                if (b0 < 0) b0 = b;
+                else if (b1 < 0 && ((b ^ b0) & 1)) b1 = b;
+                else return false;
+            }
+        }
+    }
+    return true;
+}
+
+// The k_gram_v layout of every pulsar of the context (the per-pulsar records are shared by
+// all batches, so those outside this one are laid out too): the DMX slots fill the [T | r]
+// row tiles (+16 if needed).  A pulsar off the path keeps the slot count and width it last had.
+static std::vector<VgChoice> plan_vgram(const pint_ctx* ctx, int nsplit, int force_ntr) {
+    std::vector<VgChoice> out(ctx->psrs.size());
+    for (size_t pi = 0; pi < ctx->psrs.size(); pi++) {
+        const PsrHost& ph = ctx->psrs[pi];
+        const PsrDev& d = ph.dev;
+        VgChoice& v = out[pi];
+        v = VgChoice{0, 0, d.vns, d.vkp, false};
+        if (!vg_ok(ctx, ph)) continue;
+        const int wt = d.red0c + 1, R = d.Kd - d.red0c;
+        const int ntr = first_ntr(ph, std::max((wt + 15) / 16, std::min(3, force_ntr)), nsplit);
+        if (!ntr) continue;
+        v.vg = 1;
+        v.vns = 16 * ntr - wt;
+        v.vkp = (16 * ntr + R + 15) / 16 * 16;
+        v.reslot = ph.dslot_ns != v.vns;  // the rows' slots, so k_gram_v does no modulo
+        // VB only with an all-slot row tile to drop (the [T | r] columns leave >= 16 slots)
+        // (a pulsar that fails its row test leaves the vg path: with an all-slot row tile
+        // k_gram_v takes the binned body, so vg without VB is not a layout the kernel knows)
+        if (ctx->vbin && v.vkp <= 96 && v.vns >= 16) v.vg = v.vb = vb_rows_ok(ph, nsplit) ? 1 : 0;
+    }
+    return out;
+}
+
+// The instances' offsets into the batch's buffers, the totals, and the block lists of the
+// evaluation (by block kind) and of the residual pass.  Reads L.nsplit, L.efz and L.vg.
+static void layout_instances(const pint_ctx* ctx, int ninst, const int32_t* inst_psr, BatchLayout& L) {
+    const int nsplit = L.nsplit;
+    std::vector<int> bti[PINT_NBLK], btr[PINT_NBLK];
+    L.inst.resize(ninst);
+    for (int k = 0; k < ninst; k++) {
+        const int p = inst_psr[k];
+        const PsrHost& ph = ctx->psrs[p];
+        const VgChoice& v = L.vg[p];
+        InstDev& I = L.inst[k];
+        I.psr = p;
+        I.n = ph.n;
+        I.spec = nullptr;
+        I.runs = nullptr;
+        I.ts = ph.spec.tstride;
+        I.nrun = ph.dev.nrun;
+        I.K = ph.K;
+        I.Kp = ph.dev.Kp;
+        I.toff = L.tot_table;
+        I.roff = L.tot_rows;
+        I.moff = L.tot_m;
+        I.goff = L.tot_g;
+        I.soff = L.tot_s;
+        I.coff = L.tot_c;
+        I.cvoff = L.tot_cv;
+        I.eoff = L.tot_e;
+        I.epoff = L.tot_ep;
+        I.ooff = L.tot_out;
+        I.sdoff = L.tot_sd;
+        I.ddoff = L.tot_dd;
+        I.vgoff = L.vgoff;
+        I.vboff = L.vboff;
+        I.xwoff = L.xwoff;
+        if (v.vg) {
+            L.vgoff += (long)nsplit * v.vns * (ph.dev.Kd + 3);
+            if (v.vb) L.vboff += (long)nsplit * GW * v.vns * 128;
+            L.n_vg++;
+        } else if (ph.dev.dsplit) {
+            L.any_dmx_rows = true;
+        }
+        if (ph.dev.dsplit) {
+            L.tot_sd += (long)ph.dev.ndc * ph.dev.Kpd;
+            L.tot_dd += ph.dev.ndc;
+            const long nbd = (ph.dev.Kd + 15) / 16, nbk = (ph.dev.ndc + 15) / 16;
+            L.xwoff += (nbd * (nbd + 1) / 2 + nbd * nbk) * 256 + (nbd + 3 * nbk) * 16 + schur_xw_extra(nbd, nbk);
+            L.max_ndc = std::max(L.max_ndc, ph.dev.ndc);
+        }
+        I.self = k;
+        I.rb0 = (long)L.rblk_inst.size();
+        I.nrb = std::max(1, (ph.n + RES_RB - 1) / RES_RB);
+        for (int b = 0; b < I.nrb; b++) L.rblk_inst.push_back(k);
+        L.tot_e += (long)ph.dev.nep * I.Kp;
+        L.tot_ep += ph.dev.nep;
+        L.max_nep = std::max(L.max_nep, ph.dev.nep);
+        L.tot_cv += (long)ph.spec.ncol * ph.spec.ncol;
+        L.tot_table += ph.spec.tstride;
+        int bt = ph.spec.binary;
+        if (PINT_SPEC_NFB(ph.spec) > 0)  // the FBn orbit: its own block kind, so its own build and launch
+            bt = bt == PINT_BIN_ELL1 ? PINT_BLK_FB_ELL1
+                                     : (bt == PINT_BIN_DD ? PINT_BLK_FB_DD : (bt == PINT_BIN_ELL1H ? PINT_BLK_FB_ELL1H : PINT_BLK_FB_BT));
+        if (L.efz) {  // EF_ROWS rows per block (+ row 0 and the TZR row on its last lanes)
+            I.eb0 = L.ebn;
+            I.neb = std::max(1, (ph.n + EF_ROWS - 1) / EF_ROWS);
+            L.ebn += I.neb;
+            for (int r0 = 0; r0 < std::max(1, ph.n); r0 += EF_ROWS) {
+                bti[bt].push_back(k);
+                btr[bt].push_back(r0);
+            }
+        } else {
+            I.eb0 = 0;
+            I.neb = 0;
+            for (int r0 = 0; r0 <= ph.n; r0 += 256) {
+                bti[bt].push_back(k);
+                btr[bt].push_back(r0);
+            }
+        }
+        L.tot_rows += ph.n + 1;
+        L.tot_m += (long)ph.n * ph.K;
+        L.tot_g += (long)(nsplit + 1) * I.Kp * I.Kp;  // + ECORR Schur partial
+        L.tot_s += (long)(ph.K + 1) * (ph.K + 1);
+        L.tot_c += ph.K + 1;
+        L.tot_out += ph.n;
+        L.maxK = std::max(L.maxK, ph.K);
+        L.maxn = std::max(L.maxn, ph.n);
+        L.max_ts = std::max(L.max_ts, ph.spec.tstride);
+    }
+    for (int t = 0; t < PINT_NBLK; t++) {
+        L.blk_off[t] = (int)L.blk_inst.size();
+        L.blk_inst.insert(L.blk_inst.end(), bti[t].begin(), bti[t].end());
+        L.blk_row0.insert(L.blk_row0.end(), btr[t].begin(), btr[t].end());
+    }
+    L.blk_off[PINT_NBLK] = (int)L.blk_inst.size();
+    L.nblk = L.blk_off[3];  // k_eval_mix covers the isolated, ELL1 and DD blocks
+}
+
+// k_gram's launch groups and order in one layout: 0 full, 1 compact, 2 compact on k_gram_v
+static GramOrder gram_order(const pint_ctx* ctx, const BatchLayout& L, int lay, int ncu) {
+    const int ninst = (int)L.inst.size();
+    // bucket the instances by launch key in one pass (a grid batch has ~10^5 instances)
+    const int maxT = lay == 2 ? 29 : GMAXT_ALL;
+    std::vector<std::vector<int>> bucket(maxT + 1);
+    std::vector<int> bkp(maxT + 1, 16);
+    for (int k = 0; k < ninst; k++) {
+        const InstDev& I = L.inst[k];
+        const PsrDev& pd = ctx->psrs[I.psr].dev;
+        const VgChoice& v = L.vg[I.psr];
+        if (lay == 1 && pd.dsplit && v.vg) continue;
+        if (lay == 2 && !(pd.dsplit && v.vg)) continue;
+        const int kp = lay == 2 ? v.vkp : ((lay && pd.dsplit) ? pd.Kpd : I.Kp);
+        const int nt = kp / 16;
+        int tT = (nt * (nt + 1) / 2 + GWAVES - 1) / GWAVES;
+        if (lay == 2) {  // k_gram_v template key: row tiles (1..3) x column tiles (ntr..7)
+            const int ntr = (pd.red0c + 1 + v.vns) / 16;
+            tT = 10 * (ntr - 1) + nt;
+        }
+        if (lay < 2 && ctx->small && kp <= 32 && I.n <= GS_MAXN) tT = 0;  // k_gram_s
+        if (tT < (lay < 2 ? 0 : 1) || tT > maxT) continue;
+        bucket[tT].push_back(k);
+        if (kp > bkp[tT]) bkp[tT] = kp;
+    }
+    if (lay == 2) {
+        // heaviest first within a launch (MFMAs per k-step x rows): the light blocks fill
+        // the tail of the second resident round
+        auto cost = [&](int k) {
+            const PsrDev& pd = ctx->psrs[L.inst[k].psr].dev;
+            const VgChoice& v = L.vg[L.inst[k].psr];
+            const int ntr = (pd.red0c + 1 + v.vns) / 16, ntc = v.vkp / 16;
+            const int nsk = ntr - (pd.red0c + 1 + 15) / 16;
+            int t = v.vb ? 1 : 0;
+            for (int ti = 0; ti < ntr; ti++)
+                for (int tj = ti; tj < ntc; tj++)
+                    if (!(ti >= ntr - nsk && (tj < ntr || v.vb))) t++;
+            // MFMA tiles per k-step, and the timing columns loaded and staged (measured on
+            // the bench PTA: ~4 columns cost one tile)
+            return (long)(4 * t + pd.red0c + 1) * L.inst[k].n;
+        };
+        std::vector<long> ck(ninst, 0);
+        for (auto& b : bucket) {
+            for (int k : b) ck[k] = cost(k);
+            std::stable_sort(b.begin(), b.end(), [&](int x, int y) { return ck[x] > ck[y]; });
+            // two k_gram_v workgroups share a CU, and the dispatcher gives workgroup w and
+            // w + ncu (roughly) the same CU in the first resident round: pair the heaviest
+            // instances (first ncu workgroups) with the lightest (next ncu), then the rest
+            // heaviest first (PINT_GV_PAIR=0: plain heaviest-first order)
+            const int k1 = ncu / std::max(1, L.nsplit);
+            const bool uniform = b.empty() || ck[b.front()] == ck[b.back()];  // (nothing to pair)
+            if (ctx->gv_pair && !uniform && k1 > 0 && (int)b.size() > 2 * k1) {
+                std::vector<int> o(b.begin(), b.begin() + k1);
+                o.insert(o.end(), b.rbegin(), b.rbegin() + k1);
+                o.insert(o.end(), b.begin() + k1, b.end() - k1);
+                b.swap(o);
+            }
+        }
+    }
+    GramOrder o;
+    o.ident = true;  // the launch order is the instance order (e.g. a grid's points)
+    for (int T = 0; T <= maxT; T++) {
+        if (bucket[T].empty()) continue;
+        o.groups.push_back(KpGroup{T, (int)o.order.size(), (int)bucket[T].size(), bkp[T]});
+        for (int k : bucket[T]) {
+            o.ident = o.ident && k == (int)o.order.size();
+            o.order.push_back(k);
+        }
+    }
+    o.ident = o.ident && (int)o.order.size() == ninst;
+    return o;
+}
+
+// the post-fit Woodbury dots fused into the residual pass (k_resid2 tiles, k_rsum): every
+// instance's noise basis a PLRedNoise harmonic series of < 64 modes (no PLDMNoise).  Returns
+// the dots' stride per instance, 0 without the fusion.
+static int wfuse_stride(const pint_ctx* ctx, int ninst, const int32_t* inst_psr) {
+    int R = 0;
+    for (int k = 0; k < ninst; k++) {
+        const pint_spec_t& sp = ctx->psrs[inst_psr[k]].spec;
+        R = std::max(R, 2 * sp.nred);
+        if (sp.dmn0 < sp.nred || sp.nred > 63) return 0;
+    }
+    // (R = 0: no tile to form -- a WLS batch's post-fit pass would write 2 KB of zeros per
+    // residual block; 1^T W r then comes from k_wdot if a GLS chi2 is asked for)
+    return R > 0 ? R + 2 : 0;
+}
+
+// The layout of the batch of ninst instances of the pulsars inst_psr on a chip of ncu CUs.
+static BatchLayout plan_batch(const pint_ctx* ctx, int ninst, const int32_t* inst_psr, int ncu) {
+    BatchLayout L{};
+    if ((L.err = batch_refusal(ctx, ninst, inst_psr))) return L;
+    int maxN = 0;
+    for (int k = 0; k < ninst; k++) maxN = std::max(maxN, ctx->psrs[inst_psr[k]].n);
+    // the fused residual pass for batches off the small-instance path (whose one-wave
+    // residual kernels serve instances of <= RES_SMALLN rows)
+    // (not for a batch with glitches: their phase is added after the evaluation, by k_glitch)
+    // nor with any pass after the evaluation: k_wavex and k_fdjump move the delay and the phase,
+    // k_glitch and k_phase_terms add phase, all after the evaluation's blocks have finished
+    L.post = batch_post(ctx, ninst, inst_psr);
+    L.efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && L.post == 0;
+    const long slots = gram_slots(ctx, ninst, inst_psr, ncu);
+    L.nsplit = choose_nsplit(ninst, maxN, slots);
+    L.force_ntr = choose_force_ntr(ctx, ninst, inst_psr, L.nsplit, slots);
+    L.vg = plan_vgram(ctx, L.nsplit, L.force_ntr);
+    L.vb_on = ctx->vbin;
+    layout_instances(ctx, ninst, inst_psr, L);
+    {
+        std::vector<char> seen(ctx->psrs.size(), 0);
+        for (int k = 0; k < ninst; k++)
+            if (!seen[inst_psr[k]]) {
+                seen[inst_psr[k]] = 1;
+                L.upsr.push_back(inst_psr[k]);
+            }
+    }
+    for (int pi : L.upsr) {
+        const pint_spec_t& sp = ctx->psrs[pi].spec;
+        L.sw = L.sw || sp.o_NE_SW >= 0;
+        L.any_dmn = L.any_dmn || sp.dmn0 < sp.nred;
+    }
+    for (int lay = 0; lay < 3; lay++) L.order[lay] = gram_order(ctx, L, lay, ncu);
+    L.wstride = wfuse_stride(ctx, ninst, inst_psr);
+    L.wfuse = L.wstride > 0 && !L.rblk_inst.empty();
+    return L;
+}
+
+// The batch's buffers: one table for the allocating loop (commit_batch, in this order) and
+// for free_instances, which reads the pointers alone (the counts of an empty layout mean
+// nothing).  Not here: what other calls allocate on demand (free_instances lists those).
+struct BatchBuf {
+    void** p;
+    size_t elt, count;
+    bool zero;  // zero-filled on the kernel stream
+    bool on;    // allocated for this layout
+};
+static std::vector<BatchBuf> batch_buffers(pint_ctx* ctx, const BatchLayout& L) {
+    std::vector<BatchBuf> t;
+    auto add = [&](auto*& p, long count, bool zero = false, bool on = true) {
+        t.push_back(BatchBuf{(void**)&p, sizeof(*p), (size_t)count, zero, on});
+    };
+    auto min1 = [](long n) { return std::max<long>(1, n); };
+    constexpr int NS = pint_ctx::NSLOT;
+    const long ninst = (long)L.inst.size(), nrb = (long)L.rblk_inst.size();
+    add(ctx->d_inst, ninst);
+    // (a launch order equal to the instance order is d_inst itself: the commit points it there)
+    InstDev** sorted[3] = {&ctx->d_inst_sorted, &ctx->d_inst_sorted_c, &ctx->d_inst_sorted_v};
+    for (int lay = 0; lay < 3; lay++) add(*sorted[lay], min1((long)L.order[lay].order.size()), false, !L.order[lay].ident);
+    add(ctx->d_Sdp, min1(L.vgoff));
+    add(ctx->d_BFp, min1(L.vboff));
+    for (int sl = 0; sl < NS; sl++) add(ctx->d_xw_s[sl], L.xwoff, false, L.xwoff > 0 && L.xwoff <= (1L << 28));
+    add(ctx->d_TSp, min1(ninst * L.nsplit * 4 * VTRIG));
+    add(ctx->d_TS, min1(ninst * 4 * VTRIG));
+    add(ctx->d_blk_inst, (long)L.blk_inst.size());
+    add(ctx->d_blk_row0, (long)L.blk_row0.size());
+    add(ctx->d_rblk_inst, min1(nrb));
+    add(ctx->d_rpart, 3 * min1(nrb));
+    add(ctx->d_epart, 2 * min1(L.ebn));
+    add(ctx->d_wtile, 256 * nrb, false, L.wfuse);
+    add(ctx->d_wpart, ninst * L.wstride, false, L.wfuse);  // (pint_chi2_gls grows it on demand: wpart_cap)
+    add(ctx->d_tables, L.tot_table);
+    add(ctx->d_phhi, L.tot_rows);
+    add(ctx->d_phlo, L.tot_rows);
+    add(ctx->d_ftay, L.tot_rows);
+    add(ctx->d_delay, L.tot_rows);
+    add(ctx->d_swg, L.tot_rows, false, L.sw);
+    add(ctx->d_M, min1(L.tot_m));
+    add(ctx->d_rt, L.tot_out);
+    add(ctx->d_rp, L.tot_out);
+    add(ctx->d_chi2, ninst);
+    add(ctx->d_istatus, ninst, true);
+    add(ctx->d_rscr, RSCR * ninst);
+    for (int sl = 0; sl < NS; sl++) add(ctx->d_chi2g_s[sl], ninst);
+    add(ctx->d_lognorm, ninst);
+    for (int sl = 0; sl < NS; sl++) add(ctx->d_chi2lin_s[sl], ninst);
+    add(ctx->d_G, L.tot_g);
+    add(ctx->d_colsq, L.tot_c * L.nsplit);
+    add(ctx->d_work, L.tot_s);
+    for (int sl = 0; sl < NS; sl++) add(ctx->d_cov_s[sl], min1(L.tot_cv));
+    add(ctx->d_sigL, L.tot_s);
+    for (int sl = 0; sl < NS; sl++) {
+        // the per-instance slot past the last column (K+1 stride) is never written by a solve
+        add(ctx->d_dpars_s[sl], L.tot_c, true);
+        add(ctx->d_errs_s[sl], L.tot_c, true);
+    }
+    add(ctx->d_lam, ninst);
+    add(ctx->d_norms, L.tot_c);
+    add(ctx->d_ones, L.tot_c);
+    add(ctx->d_esum, min1(L.tot_e));
+    add(ctx->d_eD, min1(L.tot_ep));
+    add(ctx->d_eW, min1(L.tot_ep));
+    add(ctx->d_eC, min1(L.tot_ep));
+    add(ctx->d_ecs, min1(L.tot_ep));
+    add(ctx->d_ic, ninst);
+    add(ctx->d_dmxv, min1(L.tot_out));
+    add(ctx->d_dfac, L.any_dmn ? min1(L.tot_out) : 1);
+    add(ctx->d_Sd, min1(L.tot_sd));
+    add(ctx->d_DD, min1(L.tot_dd));
+    add(ctx->d_DCS, min1(L.tot_dd));
+    return t;
+}
+
+// The state of a batch that nothing has run on yet: no captured graph, no constants, phases
+// or snapshot of the tables, nothing deferred, no copy in flight.  keep_red: the red-noise
+// columns of the design matrix stay as written -- pint_set_grid's reuse of the resident batch,
+// whose d_M and TOAs are the same (a fresh batch's d_M is new memory).
+static void reset_batch_state(pint_ctx* ctx, bool keep_red) {
+    for (int k = 0; k < pint_ctx::NSLOT; k++) {
+        if (ctx->graph_exec_s[k]) hipGraphExecDestroy(ctx->graph_exec_s[k]);
+        if (ctx->graph_s[k]) hipGraphDestroy(ctx->graph_s[k]);
+        ctx->graph_exec_s[k] = nullptr;
+        ctx->graph_s[k] = nullptr;
+    }
+    ctx->ic_valid = ctx->ic0_valid = false;
+    ctx->phases_valid = false;
+    ctx->restore_pending = ctx->chi2_pending = ctx->cov_pending = false;
+    ctx->r2_pending = false;
+    ctx->wtile_valid = false;
+    ctx->chi2_dst = nullptr;
+    if (!keep_red) ctx->red_valid[0] = ctx->red_valid[1] = 0;
+    clear_copy_pend(ctx);
+}
+
 static void free_instances(pint_ctx* ctx) {
     // the buffers go back to the device cache, where another context may take them
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
@@ -7559,39 +8091,17 @@ static void free_instances(pint_ctx* ctx) {
     dfree((void*&)ctx->d_shr);
     ctx->shr_cap = 0;
     ctx->spin_grid = 0;
-    for (int sl = 0; sl < pint_ctx::NSLOT; sl++) {
-        void** pss[] = {(void**)&ctx->d_chi2lin_s[sl], (void**)&ctx->d_dpars_s[sl], (void**)&ctx->d_errs_s[sl],
-                        (void**)&ctx->d_cov_s[sl], (void**)&ctx->d_chi2g_s[sl], (void**)&ctx->d_xw_s[sl]};
-        for (auto p : pss) dfree(*p);
-    }
-    void** ps[] = {(void**)&ctx->d_inst, (void**)&ctx->d_inst_sorted, (void**)&ctx->d_blk_inst, (void**)&ctx->d_blk_row0, (void**)&ctx->d_tables,
-                   (void**)&ctx->d_phhi, (void**)&ctx->d_phlo, (void**)&ctx->d_ftay, (void**)&ctx->d_delay, (void**)&ctx->d_swg,
-                   (void**)&ctx->d_M, (void**)&ctx->d_rt, (void**)&ctx->d_rp, (void**)&ctx->d_chi2, (void**)&ctx->d_istatus, (void**)&ctx->d_rscr,
-                   (void**)&ctx->d_G, (void**)&ctx->d_colsq,
-                   (void**)&ctx->d_work, (void**)&ctx->d_sigL,
-                   (void**)&ctx->d_lam, (void**)&ctx->d_lognorm,
-                   (void**)&ctx->d_eigw,
-                   (void**)&ctx->d_degv, (void**)&ctx->d_ndeg, (void**)&ctx->d_esum, (void**)&ctx->d_eD,
-                   (void**)&ctx->d_eW, (void**)&ctx->d_eC, (void**)&ctx->d_ecs, (void**)&ctx->d_wpart, (void**)&ctx->d_ic, (void**)&ctx->d_ic0,
-                   (void**)&ctx->d_dmxv, (void**)&ctx->d_Sd, (void**)&ctx->d_DD, (void**)&ctx->d_DCS,
-                   (void**)&ctx->d_dfac, (void**)&ctx->d_inst_sorted_c, (void**)&ctx->d_inst_sorted_v, (void**)&ctx->d_Sdp,
-                   (void**)&ctx->d_BFp, (void**)&ctx->d_TSp, (void**)&ctx->d_TS, (void**)&ctx->d_rblk_inst, (void**)&ctx->d_rpart, (void**)&ctx->d_epart,
-                   (void**)&ctx->d_noise, (void**)&ctx->d_tables0,
-                   (void**)&ctx->d_wtile, (void**)&ctx->d_norms, (void**)&ctx->d_ones};
+    for (const BatchBuf& b : batch_buffers(ctx, BatchLayout{})) dfree(*b.p);
+    // ... and what other calls allocated on demand for this batch: k_eig's scratch, the
+    // snapshot's constants and tables, the noise realisations
+    void** ps[] = {(void**)&ctx->d_eigw, (void**)&ctx->d_degv, (void**)&ctx->d_ndeg, (void**)&ctx->d_ic0,
+                   (void**)&ctx->d_noise, (void**)&ctx->d_tables0};
     for (auto p : ps) dfree(*p);
     ctx->d_dpars = ctx->d_errs = ctx->d_cov = ctx->d_chi2lin = ctx->d_xw = ctx->d_chi2g = nullptr;
-    clear_copy_pend(ctx);
     ctx->noise_cap = 0;
     ctx->tables0_cap = 0;
-    ctx->ic0_valid = false;
-    ctx->restore_pending = false;
-    ctx->wfuse = ctx->wtile_valid = false;
-    for (int k = 0; k < pint_ctx::NSLOT; k++) {
-        if (ctx->graph_exec_s[k]) hipGraphExecDestroy(ctx->graph_exec_s[k]);
-        if (ctx->graph_s[k]) hipGraphDestroy(ctx->graph_s[k]);
-        ctx->graph_exec_s[k] = nullptr;
-        ctx->graph_s[k] = nullptr;
-    }
+    ctx->wfuse = false;
+    reset_batch_state(ctx, false);
     ctx->ninst = 0;
     ctx->wpart_cap = 0;
     ctx->eig_cap = 0;
@@ -8287,20 +8797,9 @@ static int grid_batch(pint_ctx* ctx, int psr, int npts) {
         HIPCHK(hipStreamSynchronize(ctx->cstream));
         HIPCHK(hipStreamSynchronize(ctx->sstream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        clear_copy_pend(ctx);
         dfree((void*&)ctx->d_tables0);  // (a snapshot of the previous points)
         ctx->tables0_cap = 0;
-        ctx->ic_valid = ctx->ic0_valid = false;
-        ctx->phases_valid = false;
-        ctx->restore_pending = ctx->chi2_pending = ctx->cov_pending = false;
-        ctx->wtile_valid = false;
-        ctx->chi2_dst = nullptr;
-        for (int k = 0; k < pint_ctx::NSLOT; k++) {
-            if (ctx->graph_exec_s[k]) hipGraphExecDestroy(ctx->graph_exec_s[k]);
-            if (ctx->graph_s[k]) hipGraphDestroy(ctx->graph_s[k]);
-            ctx->graph_exec_s[k] = nullptr;
-            ctx->graph_s[k] = nullptr;
-        }
+        reset_batch_state(ctx, true);  // (d_M stays: its red-noise columns are the same TOAs')
         HIPCHK(hipMemsetAsync(ctx->d_istatus, 0, sizeof(int) * ctx->ninst, ctx->stream));
         HIPCHK(hipMemsetAsync(ctx->d_cov, 0, sizeof(double) * std::max<long>(1, ctx->tot_cv), ctx->stream));
         ctx->n_batch_reuse++;
@@ -8428,194 +8927,25 @@ int pint_set_points(pint_ctx* ctx, int psr, int npts, const double* base, int nv
     return PINT_OK;
 }
 
-static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr, const double* tables) {
-    if (!ctx || ninst <= 0) return PINT_E_INVALID;
-    ctx->grid_valid = false;  // (pint_set_grid marks its own batch afterwards)
-    ctx->points_valid = false;
-    ctx->tables_fresh = false;
-    ctx->r2_pending = false;
-    hipSetDevice(ctx->device);
-    if (ctx->psrs_dirty && refresh_psrs(ctx)) return PINT_E_HIP;
-    if (flush_setup(ctx)) return PINT_E_HIP;  // the uploads' red-noise set-up, one batch
-    if (int rc = flush_cq_now(ctx)) return rc;  // (their buffers are freed below, after the streams drain)
-    free_instances(ctx);
-    ctx->inst.resize(ninst);
-    long toff = 0, roff = 0, moff = 0, goff = 0, soff = 0, coff = 0, out = 0, cvoff = 0, eoff = 0, epoff = 0;
-    long sdoff = 0, ddoff = 0;
-    int max_nep = 0, max_ndc = 0;
-    std::vector<int> bti[PINT_NBLK], btr[PINT_NBLK];
-    std::vector<int> rbi;
-    int maxK = 0, maxN = 0;
-    for (int k = 0; k < ninst; k++) {
-        int p = inst_psr[k];
-        if (p < 0 || p >= (int)ctx->psrs.size()) { ctx->err = "bad pulsar id"; return PINT_E_INVALID; }
-        if (ctx->psrs[p].n > maxN) maxN = ctx->psrs[p].n;
-    }
-    // the fused residual pass for batches off the small-instance path (whose one-wave
-    // residual kernels serve instances of <= RES_SMALLN rows)
-    // (not for a batch with glitches: their phase is added after the evaluation, by k_glitch)
-    // nor with any pass after the evaluation: k_wavex and k_fdjump move the delay and the phase,
-    // k_glitch and k_phase_terms add phase, all after the evaluation's blocks have finished
-    ctx->post = 0;
-    for (int k = 0; k < ninst; k++) {
-        const PsrHost& e = ctx->psrs[inst_psr[k]];
-        const PsrDev& d = e.dev;
-        if (d.nwx + d.ndmwx > 0) ctx->post |= POST_WAVEX;
-        if (d.ncm + d.ncmwx > 0) ctx->post |= POST_WAVEX | POST_CHROM;  // (the same pass, in its chromatic build)
-        if (d.nfdj + d.nfdjdm > 0) ctx->post |= POST_FDJUMP;
-        if (e.spec.nglitch > 0) ctx->post |= POST_GLITCH;
-        if (d.npw + d.nwave + d.nifunc > 0) ctx->post |= POST_PHASE_TERMS;
-    }
-    ctx->efz = ctx->efuse && !(ctx->small && maxN <= RES_SMALLN) && ctx->post == 0;
-    long ebn = 0;
-    // N-split for the Gram so the launch fills the 256 CUs
-    // choose the split count that minimises (workgroup rounds) / nsplit, i.e. the k_gram
-    // makespan with one 1024-thread workgroup resident per CU, with >= 4 chunks per split
-    int ncu = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0)
-            ncu = prop.multiProcessorCount;
-    }
-    int maxsplit = (maxN + 4 * GCH - 1) / (4 * GCH);
-    if (maxsplit < 1) maxsplit = 1;
-    // Resident Gram workgroups per CU: k_gram runs one per CU, k_gram_v GWG; the batch's
-    // majority path decides
-    long nvgc = 0;
-    for (int k = 0; k < ninst; k++) {
-        const PsrHost& ph = ctx->psrs[inst_psr[k]];
-        const PsrDev& d = ph.dev;
-        nvgc += (ctx->vgram && d.dsplit && d.dcontig && d.nep == 0 && ph.spec.nred <= VTRIG / 2 - 1 &&
-                 d.red0c + 1 <= VMAXR0) ? 1 : 0;
-    }
-    const long slots = (long)ncu * (2 * nvgc > ninst ? GWG : 1);
-    // A batch too small to fill the chip even at the finest split (a single fit, a few
-    // pulsars) is latency-bound: splits of 128 rows leave each workgroup two chunks while
-    // k_greduce sums hundreds of partials per Gram element.  Keep >= 512 rows per split there.
-    if ((long)ninst * maxsplit < slots) maxsplit = std::max(1, std::min(maxsplit, (maxN + 511) / 512));
-    // (smallest split count within 3% of the best makespan: each split adds a partial
-    // Gram that k_greduce must sum)
-    double best = 1e30;
-    for (int ns = 1; ns <= maxsplit && ns <= 4096; ns++) {
-        long blocks = (long)ninst * ns;
-        double cost = (double)((blocks + slots - 1) / slots) / ns;
-        if (cost < best) best = cost;
-    }
-    int nsplit = 1;
-    for (int ns = 1; ns <= maxsplit && ns <= 4096; ns++) {
-        long blocks = (long)ninst * ns;
-        double cost = (double)((blocks + slots - 1) / slots) / ns;
-        if (cost <= best * 1.03) { nsplit = ns; break; }
-    }
-    // (measured on the 68-pulsar PTA, round 4: 7 splits -- one round of workgroups, many CUs
-    // with one -- 0.120 ms of k_gram_v, 8: 0.147, 11: 0.104, this model's 15: 0.089-0.093)
-    if (const char* e = getenv("PINT_NSPLIT")) {  // (diagnostic sweeps: a fixed split count)
-        const int v = atoi(e);
-        if (v >= 1) nsplit = std::min(v, std::max(1, (maxN + 63) / 64));
-    }
-    ctx->nsplit = nsplit;
-    ctx->red_valid[0] = ctx->red_valid[1] = 0;
-    ctx->ic_valid = false;
-    ctx->phases_valid = false;
-    // vg compact path (k_gram_v): contiguous DMX bins, no ECORR, nred <= 31, <= 47
-    // timing columns; the DMX slots fill the [T | r] row tiles (+16 if needed) such that the
-    // bins of every N-split are distinct mod vns; LDS width <= VMAXKP
-    auto vg_ok = [&](const PsrHost& ph) {
-        const PsrDev& d = ph.dev;
-        return ctx->vgram && d.dsplit && d.dcontig && d.nep == 0 && ph.spec.nred <= VTRIG / 2 - 1 &&
-               ph.spec.dmn0 >= ph.spec.nred &&  // PLDMNoise: stored, per-TOA scaled basis
-               d.red0c + 1 <= VMAXR0;
-    };
-    auto slots_ok = [&](const PsrHost& ph, int ntr) {  // bins of every split distinct mod ns
-        const PsrDev& d = ph.dev;
-        const int wt = d.red0c + 1, R = d.Kd - d.red0c;
-        const int ns = 16 * ntr - wt, kpv = (16 * ntr + R + 15) / 16 * 16;
-        if (ns < 1 || kpv > VMAXKP) return false;
-        long per = (ph.n + nsplit - 1) / nsplit;
-        per = (per + 3) / 4 * 4;
-        for (int sp = 0; sp < nsplit; sp++) {
-            const long i0 = sp * per, i1 = std::min<long>(i0 + per, ph.n);
-            std::vector<char> seen(ns, 0);
-            for (int a = 0; a < d.ndc; a++) {
-                if (ph.dhi[a] <= ph.dlo[a] || ph.dlo[a] >= i1 || ph.dhi[a] <= i0) continue;
-                if (seen[a % ns]) return false;
-                seen[a % ns] = 1;
-            }
-        }
-        return true;
-    };
-    // A batch whose Gram workgroups fit one resident round (a few pulsars: the per-rank shard
-    // of a PTA over several GPUs) is latency-bound, and every distinct k_gram_v tile shape is
-    // a launch of its own, in sequence: there all vg pulsars take the largest row-tile count
-    // any of them needs (more padding MFMAs, one launch)
-    int force_ntr = 0;
-    if ((long)ninst * nsplit <= slots) {
-        std::vector<char> inb(ctx->psrs.size(), 0);
-        for (int k = 0; k < ninst; k++) inb[inst_psr[k]] = 1;
-        for (size_t p = 0; p < ctx->psrs.size(); p++) {
-            const PsrHost& ph = ctx->psrs[p];
-            if (!inb[p] || !vg_ok(ph)) continue;
-            const int wt = ph.dev.red0c + 1;
-            for (int ntr = (wt + 15) / 16; ntr <= std::min(3, (wt + 15) / 16 + 2); ntr++)
-                if (slots_ok(ph, ntr)) { force_ntr = std::max(force_ntr, ntr); break; }
-        }
-    }
-    // the rows' DMX slot ids of every pulsar whose slot count changed, staged into one
-    // allocation and one copy after the loop (a PTA: 68 uploads of 40 KB each, ~0.1 ms apiece)
+// The pulsars' k_gram_v choices written to their records, and the rows' DMX slot ids of every
+// pulsar whose slot count changed: staged into one allocation and one copy (a PTA: 68 uploads
+// of 40 KB each, ~0.1 ms apiece)
+static int commit_vgram(pint_ctx* ctx, const BatchLayout& L) {
     std::vector<std::pair<size_t, size_t>> slot_up;  // (pulsar, offset in slot_host)
     std::vector<int32_t> slot_host;
     for (size_t pi = 0; pi < ctx->psrs.size(); pi++) {
         PsrHost& ph = ctx->psrs[pi];
-        PsrDev& d = ph.dev;
-        d.vg = 0;
-        d.vb = 0;
-        if (!vg_ok(ph)) continue;
-        long per = (ph.n + nsplit - 1) / nsplit;
-        per = (per + 3) / 4 * 4;
-        const int wt = d.red0c + 1, R = d.Kd - d.red0c;
-        const int ntr0 = std::max((wt + 15) / 16, std::min(3, force_ntr));
-        for (int ntr = ntr0; ntr <= std::min(3, (wt + 15) / 16 + 2); ntr++) {
-            const int ns = 16 * ntr - wt, kpv = (16 * ntr + R + 15) / 16 * 16;
-            if (!slots_ok(ph, ntr)) continue;
-            {
-                d.vg = 1;
-                d.vns = ns;
-                d.vkp = kpv;
-                if (ph.dslot_ns != ns) {  // the rows' slots, so k_gram_v does no modulo
-                    const size_t o = (slot_host.size() + 63) & ~(size_t)63;
-                    slot_host.resize(o + ph.n);
-                    for (int i = 0; i < ph.n; i++) slot_host[o + i] = ph.drow_host[i] >= 0 ? ph.drow_host[i] % ns : -1;
-                    slot_up.push_back({pi, o});
-                    ph.dslot_ns = ns;
-                }
-                break;
-            }
-        }
-        d.vb = 0;
-        // VB only with an all-slot row tile to drop (the [T | r] columns leave >= 16 slots)
-        if (d.vg && ctx->vbin && d.vkp <= 96 && d.vns >= 16) {
-            // VB (binned DMX x F): the 16 rows a wave takes from one chunk (split sp, quarter w,
-            // rows i0 + w QV + 16 c ..) hold at most two bins, of distinct parity (drow)
-            // (a pulsar that fails it leaves the vg path: with an all-slot row tile k_gram_v
-            // takes the binned body, so vg without VB is not a layout the kernel knows)
-            const std::vector<int>& dr = ph.drow_host;
-            for (int sp = 0; d.vg && sp < nsplit; sp++) {
-                const long i0 = std::min<long>((long)sp * per, ph.n), i1 = std::min<long>(i0 + per, ph.n);
-                const long QV = (i1 - i0 + VCH - 1) / VCH * 16;
-                for (long g = 0; d.vg && g < i1 - i0; g += 16) {  // g = w QV + 16 c
-                    const long gend = std::min<long>(g + 16, (g / QV + 1) * QV);
-                    int b0 = -1, b1 = -1;
-                    for (long r = g; r < gend && r < i1 - i0; r++) {
-                        const int b = dr[i0 + r];
-                        if (b < 0 || b == b0 || b == b1) continue;
-                        if (b0 < 0) b0 = b;
-                        else if (b1 < 0 && ((b ^ b0) & 1)) b1 = b;
-                        else d.vg = 0;
-                    }
-                }
-            }
-            d.vb = d.vg;
-        }
+        const VgChoice& v = L.vg[pi];
+        ph.dev.vg = v.vg;
+        ph.dev.vb = v.vb;
+        ph.dev.vns = v.vns;
+        ph.dev.vkp = v.vkp;
+        if (!v.reslot) continue;
+        const size_t o = (slot_host.size() + 63) & ~(size_t)63;
+        slot_host.resize(o + ph.n);
+        for (int i = 0; i < ph.n; i++) slot_host[o + i] = ph.drow_host[i] >= 0 ? ph.drow_host[i] % v.vns : -1;
+        slot_up.push_back({pi, o});
+        ph.dslot_ns = v.vns;
     }
     if (!slot_up.empty()) {
         void* p = nullptr;
@@ -8624,318 +8954,113 @@ static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr,
         ctx->psrs[slot_up[0].first].bufs.push_back(p);  // (freed with the first pulsar's buffers)
         for (auto& u : slot_up) ctx->psrs[u.first].dev.dslot = static_cast<const int32_t*>(p) + u.second;
     }
-    if (refresh_psrs(ctx)) return PINT_E_HIP;
-    long vgoff = 0, vboff = 0, xwoff = 0;
-    ctx->n_vg = 0;
-    ctx->cov_pending = false;
-    ctx->vb_on = ctx->vbin;
-    ctx->any_dmx_rows = false;
-    for (int k = 0; k < ninst; k++) {
-        int p = inst_psr[k];
-        PsrHost& ph = ctx->psrs[p];
-        InstDev& I = ctx->inst[k];
-        I.psr = p;
-        I.n = ph.n;
-        I.spec = ph.dev.spec;
-        I.runs = ph.dev.runs;
-        I.ts = ph.spec.tstride;
-        I.nrun = ph.dev.nrun;
-        I.K = ph.K;
-        I.Kp = ph.dev.Kp;
-        I.toff = toff;
-        I.roff = roff;
-        I.moff = moff;
-        I.goff = goff;
-        I.soff = soff;
-        I.coff = coff;
-        I.cvoff = cvoff;
-        I.eoff = eoff;
-        I.epoff = epoff;
-        I.ooff = out;
-        I.sdoff = sdoff;
-        I.ddoff = ddoff;
-        I.vgoff = vgoff;
-        I.vboff = vboff;
-        I.xwoff = xwoff;
-        if (ph.dev.vg) {
-            vgoff += (long)nsplit * ph.dev.vns * (ph.dev.Kd + 3);
-            if (ph.dev.vb) vboff += (long)nsplit * GW * ph.dev.vns * 128;
-            ctx->n_vg++;
-        } else if (ph.dev.dsplit) {
-            ctx->any_dmx_rows = true;
-        }
-        if (ph.dev.dsplit) {
-            sdoff += (long)ph.dev.ndc * ph.dev.Kpd;
-            ddoff += ph.dev.ndc;
-            const long nbd = (ph.dev.Kd + 15) / 16, nbk = (ph.dev.ndc + 15) / 16;
-            xwoff += (nbd * (nbd + 1) / 2 + nbd * nbk) * 256 + (nbd + 3 * nbk) * 16 + schur_xw_extra(nbd, nbk);
-            if (ph.dev.ndc > max_ndc) max_ndc = ph.dev.ndc;
-        }
-        I.self = k;
-        I.rb0 = (long)rbi.size();
-        I.nrb = std::max(1, (ph.n + RES_RB - 1) / RES_RB);
-        for (int b = 0; b < I.nrb; b++) rbi.push_back(k);
-        eoff += (long)ph.dev.nep * I.Kp;
-        epoff += ph.dev.nep;
-        if (ph.dev.nep > max_nep) max_nep = ph.dev.nep;
-        cvoff += (long)ph.spec.ncol * ph.spec.ncol;
-        toff += ph.spec.tstride;
-        int bt = ph.spec.binary;
-        if (bt < 0 || bt >= PINT_NBIN) { ctx->err = "bad binary model"; return PINT_E_INVALID; }
-        if (PINT_SPEC_NFB(ph.spec) > 0)  // the FBn orbit: its own block kind, so its own build and launch
-            bt = bt == PINT_BIN_ELL1 ? PINT_BLK_FB_ELL1
-                                     : (bt == PINT_BIN_DD ? PINT_BLK_FB_DD : (bt == PINT_BIN_ELL1H ? PINT_BLK_FB_ELL1H : PINT_BLK_FB_BT));
-        if (ctx->efz) {  // EF_ROWS rows per block (+ row 0 and the TZR row on its last lanes)
-            I.eb0 = ebn;
-            I.neb = std::max(1, (ph.n + EF_ROWS - 1) / EF_ROWS);
-            ebn += I.neb;
-            for (int r0 = 0; r0 < std::max(1, ph.n); r0 += EF_ROWS) {
-                bti[bt].push_back(k);
-                btr[bt].push_back(r0);
-            }
-        } else {
-            I.eb0 = 0;
-            I.neb = 0;
-            for (int r0 = 0; r0 <= ph.n; r0 += 256) {
-                bti[bt].push_back(k);
-                btr[bt].push_back(r0);
-            }
-        }
-        roff += ph.n + 1;
-        moff += (long)ph.n * ph.K;
-        goff += (long)(nsplit + 1) * I.Kp * I.Kp;  // + ECORR Schur partial
-        soff += (long)(ph.K + 1) * (ph.K + 1);
-        coff += ph.K + 1;
-        out += ph.n;
-        if (ph.K > maxK) maxK = ph.K;
+    return refresh_psrs(ctx) ? PINT_E_HIP : PINT_OK;
+}
+
+// The layout's scalars, instances and launch groups into the context's fields.
+static void commit_scalars(pint_ctx* ctx, BatchLayout& L) {
+    ctx->post = L.post;
+    ctx->efz = L.efz;
+    ctx->nsplit = L.nsplit;
+    ctx->n_vg = L.n_vg;
+    ctx->vb_on = L.vb_on;
+    ctx->any_dmx_rows = L.any_dmx_rows;
+    ctx->ninst = (int)L.inst.size();
+    ctx->tot_table = L.tot_table;
+    ctx->tot_rows = L.tot_rows;
+    ctx->tot_m = L.tot_m;
+    ctx->tot_g = L.tot_g;
+    ctx->tot_s = L.tot_s;
+    ctx->tot_c = L.tot_c;
+    ctx->tot_out = L.tot_out;
+    ctx->tot_cv = L.tot_cv;
+    ctx->tot_e = L.tot_e;
+    ctx->tot_ep = L.tot_ep;
+    ctx->maxK = L.maxK;
+    ctx->maxn = L.maxn;
+    ctx->max_ts = L.max_ts;
+    ctx->max_nep = L.max_nep;
+    ctx->max_ndc = L.max_ndc;
+    ctx->upsr = std::move(L.upsr);
+    for (int t = 0; t <= PINT_NBLK; t++) ctx->blk_off[t] = L.blk_off[t];
+    ctx->nblk = L.nblk;
+    ctx->nrblk = (int)L.rblk_inst.size();
+    ctx->kp_groups = std::move(L.order[0].groups);
+    ctx->kp_groups_c = std::move(L.order[1].groups);
+    ctx->kp_groups_v = std::move(L.order[2].groups);
+    ctx->wfuse = L.wfuse;
+    if (L.wfuse) ctx->wstride = L.wstride;
+    ctx->inst = std::move(L.inst);
+    for (InstDev& I : ctx->inst) {  // the pulsars' device pointers, final now that their uploads are committed
+        I.spec = ctx->psrs[I.psr].dev.spec;
+        I.runs = ctx->psrs[I.psr].dev.runs;
     }
-    ctx->ninst = ninst;
-    ctx->tot_table = toff;
-    ctx->tot_rows = roff;
-    ctx->tot_m = moff;
-    ctx->tot_g = goff;
-    ctx->tot_s = soff;
-    ctx->tot_c = coff;
-    ctx->tot_out = out;
-    ctx->tot_cv = cvoff;
-    ctx->maxK = maxK;
-    ctx->maxn = 0;
-    ctx->max_ts = 0;
-    for (const InstDev& I : ctx->inst) {
-        ctx->maxn = std::max(ctx->maxn, I.n);
-        ctx->max_ts = std::max(ctx->max_ts, ctx->psrs[I.psr].spec.tstride);
-    }
-    {
-        std::vector<char> seen(ctx->psrs.size(), 0);
-        ctx->upsr.clear();
-        for (int k = 0; k < ninst; k++)
-            if (!seen[inst_psr[k]]) {
-                seen[inst_psr[k]] = 1;
-                ctx->upsr.push_back(inst_psr[k]);
-            }
-    }
-    ctx->tot_e = eoff;
-    ctx->tot_ep = epoff;
-    ctx->max_nep = max_nep;
-    ctx->max_ndc = max_ndc;
-    std::vector<int> bi, br;
-    for (int t = 0; t < PINT_NBLK; t++) {
-        ctx->blk_off[t] = (int)bi.size();
-        bi.insert(bi.end(), bti[t].begin(), bti[t].end());
-        br.insert(br.end(), btr[t].begin(), btr[t].end());
-    }
-    ctx->blk_off[PINT_NBLK] = (int)bi.size();
-    ctx->nblk = ctx->blk_off[3];  // k_eval_mix covers the isolated, ELL1 and DD blocks
-    HIPCHK(cmalloc((void**)&ctx->d_inst, sizeof(InstDev) * ninst));
-    HIPCHK(h2d(ctx->d_inst, ctx->inst.data(), sizeof(InstDev) * ninst, nullptr, true));
-    for (int lay = 0; lay < 3; lay++) {  // k_gram launch groups: full, compact, compact + vg
-        std::vector<InstDev> sorted;
-        std::vector<KpGroup>& groups = lay == 0 ? ctx->kp_groups : (lay == 1 ? ctx->kp_groups_c : ctx->kp_groups_v);
-        groups.clear();
-        // bucket the instances by launch key in one pass (a grid batch has ~10^5 instances)
-        const int maxT = lay == 2 ? 29 : GMAXT_ALL;
-        std::vector<std::vector<int>> bucket(maxT + 1);
-        std::vector<int> bkp(maxT + 1, 16);
-        for (int k = 0; k < ninst; k++) {
-            const InstDev& I = ctx->inst[k];
-            const PsrDev& pd = ctx->psrs[I.psr].dev;
-            if (lay == 1 && pd.dsplit && pd.vg) continue;
-            if (lay == 2 && !(pd.dsplit && pd.vg)) continue;
-            const int kp = lay == 2 ? pd.vkp : ((lay && pd.dsplit) ? pd.Kpd : I.Kp);
-            const int nt = kp / 16;
-            int tT = (nt * (nt + 1) / 2 + GWAVES - 1) / GWAVES;
-            if (lay == 2) {  // k_gram_v template key: row tiles (1..3) x column tiles (ntr..7)
-                const int ntr = (pd.red0c + 1 + pd.vns) / 16;
-                tT = 10 * (ntr - 1) + nt;
-            }
-            if (lay < 2 && ctx->small && kp <= 32 && I.n <= GS_MAXN) tT = 0;  // k_gram_s
-            if (tT < (lay < 2 ? 0 : 1) || tT > maxT) continue;
-            bucket[tT].push_back(k);
-            if (kp > bkp[tT]) bkp[tT] = kp;
-        }
-        if (lay == 2) {
-            // heaviest first within a launch (MFMAs per k-step x rows): the light blocks fill
-            // the tail of the second resident round
-            auto cost = [&](int k) {
-                const PsrDev& pd = ctx->psrs[ctx->inst[k].psr].dev;
-                const int ntr = (pd.red0c + 1 + pd.vns) / 16, ntc = pd.vkp / 16;
-                const int nsk = ntr - (pd.red0c + 1 + 15) / 16;
-                int t = pd.vb ? 1 : 0;
-                for (int ti = 0; ti < ntr; ti++)
-                    for (int tj = ti; tj < ntc; tj++)
-                        if (!(ti >= ntr - nsk && (tj < ntr || pd.vb))) t++;
-                // MFMA tiles per k-step, and the timing columns loaded and staged (measured on
-                // the bench PTA: ~4 columns cost one tile)
-                return (long)(4 * t + pd.red0c + 1) * ctx->inst[k].n;
-            };
-            std::vector<long> ck(ninst, 0);
-            for (auto& b : bucket) {
-                for (int k : b) ck[k] = cost(k);
-                std::stable_sort(b.begin(), b.end(), [&](int x, int y) { return ck[x] > ck[y]; });
-                // two k_gram_v workgroups share a CU, and the dispatcher gives workgroup w and
-                // w + ncu (roughly) the same CU in the first resident round: pair the heaviest
-                // instances (first ncu workgroups) with the lightest (next ncu), then the rest
-                // heaviest first (PINT_GV_PAIR=0: plain heaviest-first order)
-                const int k1 = ncu / std::max(1, nsplit);
-                const bool uniform = b.empty() || ck[b.front()] == ck[b.back()];  // (nothing to pair)
-                if (ctx->gv_pair && !uniform && k1 > 0 && (int)b.size() > 2 * k1) {
-                    std::vector<int> o(b.begin(), b.begin() + k1);
-                    o.insert(o.end(), b.rbegin(), b.rbegin() + k1);
-                    o.insert(o.end(), b.begin() + k1, b.end() - k1);
-                    b.swap(o);
-                }
-            }
-        }
-        bool ident = true;  // the launch order is the instance order (e.g. a grid's points)
-        int nxt = 0;
-        for (int T = 0; T <= maxT; T++) {
-            if (bucket[T].empty()) continue;
-            KpGroup g{T, (int)sorted.size(), (int)bucket[T].size(), bkp[T]};
-            for (int k : bucket[T]) {
-                ident = ident && k == nxt++;
-                sorted.push_back(ctx->inst[k]);
-            }
-            groups.push_back(g);
-        }
-        InstDev*& dst = lay == 0 ? ctx->d_inst_sorted : (lay == 1 ? ctx->d_inst_sorted_c : ctx->d_inst_sorted_v);
-        if (ident && (int)sorted.size() == ninst) {
-            // one upload of the instance array serves this launch order too (a 65,536-point
-            // grid batch moved ~10 MB of InstDev per order from pageable memory, ~1 ms each)
-            dst = ctx->d_inst;
-            ctx->sorted_alias[lay] = true;
-            continue;
-        }
-        HIPCHK(cmalloc((void**)&dst, sizeof(InstDev) * std::max<size_t>(1, sorted.size())));
-        if (!sorted.empty())
-            HIPCHK(h2d(dst, sorted.data(), sizeof(InstDev) * sorted.size(), nullptr, true));
-    }
+}
+
+// Carry a layout out: the previous batch freed, the pulsars' records and the context's fields
+// written, the buffers allocated and the instance arrays and block lists uploaded.
+static int commit_batch(pint_ctx* ctx, BatchLayout& L, const double* tables) {
+    ctx->grid_valid = false;  // (pint_set_grid marks its own batch afterwards)
+    ctx->points_valid = false;
+    ctx->tables_fresh = false;
+    hipSetDevice(ctx->device);
+    if (ctx->psrs_dirty && refresh_psrs(ctx)) return PINT_E_HIP;
+    if (flush_setup(ctx)) return PINT_E_HIP;  // the uploads' red-noise set-up, one batch
+    if (int rc = flush_cq_now(ctx)) return rc;  // (their buffers are freed below, after the streams drain)
+    free_instances(ctx);  // (and reset_batch_state)
+    if (int rc = commit_vgram(ctx, L)) return rc;
+    const std::vector<BatchBuf> bufs = batch_buffers(ctx, L);  // (the counts, before the layout's vectors move)
+    commit_scalars(ctx, L);
+    const int ninst = ctx->ninst;
     if (getenv("PINT_VERBOSE")) {
         for (auto& g : ctx->kp_groups_v) fprintf(stderr, "[pint] k_gram_v group key %d: %d instances, max width %d\n", g.T, g.count, g.maxKp);
         for (size_t k = 0; k < ctx->psrs.size() && k < 4; k++) {
             const PsrDev& d = ctx->psrs[k].dev;
-            fprintf(stderr, "[pint] psr %zu: vg %d r0 %d Kd %d ns %d kpv %d ndc %d nsplit %d\n", k, d.vg, d.red0c, d.Kd, d.vns, d.vkp, d.ndc, nsplit);
+            fprintf(stderr, "[pint] psr %zu: vg %d r0 %d Kd %d ns %d kpv %d ndc %d nsplit %d\n", k, d.vg, d.red0c, d.Kd, d.vns, d.vkp, d.ndc, ctx->nsplit);
         }
     }
-    HIPCHK(cmalloc((void**)&ctx->d_Sdp, sizeof(double) * std::max<long>(1, vgoff)));
-    HIPCHK(cmalloc((void**)&ctx->d_BFp, sizeof(double) * std::max<long>(1, vboff)));
-    if (xwoff > 0 && xwoff <= (1L << 28)) {
-        for (int sl = 0; sl < pint_ctx::NSLOT; sl++) HIPCHK(cmalloc((void**)&ctx->d_xw_s[sl], sizeof(double) * xwoff));
+    for (const BatchBuf& b : bufs) {
+        if (!b.on) continue;
+        HIPCHK(cmalloc(b.p, b.elt * b.count));
+        if (b.zero) HIPCHK(hipMemsetAsync(*b.p, 0, b.elt * b.count, ctx->stream));
     }
-    HIPCHK(cmalloc((void**)&ctx->d_TSp, sizeof(double) * std::max<long>(1, (long)ninst * nsplit * 4 * VTRIG)));
-    HIPCHK(cmalloc((void**)&ctx->d_TS, sizeof(double) * std::max<long>(1, (long)ninst * 4 * VTRIG)));
-    HIPCHK(cmalloc((void**)&ctx->d_blk_inst, sizeof(int) * bi.size()));
-    HIPCHK(cmalloc((void**)&ctx->d_blk_row0, sizeof(int) * br.size()));
-    HIPCHK(h2d(ctx->d_blk_inst, bi.data(), sizeof(int) * bi.size(), nullptr, true));
-    HIPCHK(h2d(ctx->d_blk_row0, br.data(), sizeof(int) * br.size(), nullptr, true));
-    ctx->nrblk = (int)rbi.size();
-    HIPCHK(cmalloc((void**)&ctx->d_rblk_inst, sizeof(int) * std::max<size_t>(1, rbi.size())));
-    if (!rbi.empty())
-        HIPCHK(h2d(ctx->d_rblk_inst, rbi.data(), sizeof(int) * rbi.size(), nullptr, true));
-    HIPCHK(cmalloc((void**)&ctx->d_rpart, sizeof(double) * 3 * std::max<size_t>(1, rbi.size())));
-    HIPCHK(cmalloc((void**)&ctx->d_epart, sizeof(double) * 2 * std::max<long>(1, ebn)));
-    // the post-fit Woodbury dots fused into the residual pass (k_resid2 tiles, k_rsum): every
-    // instance's noise basis a PLRedNoise harmonic series of < 64 modes (no PLDMNoise)
-    {
-        bool fuse = true;
-        int R = 0;
-        for (int k = 0; k < ninst; k++) {
-            const pint_spec_t& sp = ctx->psrs[inst_psr[k]].spec;
-            R = std::max(R, 2 * sp.nred);
-            if (sp.dmn0 < sp.nred || sp.nred > 63) fuse = false;
-        }
-        // (R = 0: no tile to form -- a WLS batch's post-fit pass would write 2 KB of zeros per
-        // residual block; 1^T W r then comes from k_wdot if a GLS chi2 is asked for)
-        ctx->wfuse = fuse && R > 0 && !rbi.empty();
-        ctx->wtile_valid = false;
-        if (ctx->wfuse) {
-            HIPCHK(cmalloc((void**)&ctx->d_wtile, sizeof(double) * 256 * rbi.size()));
-            const size_t need = (size_t)ninst * (R + 2);
-            if (need > ctx->wpart_cap) {
-                dfree((void*&)ctx->d_wpart);
-                HIPCHK(cmalloc((void**)&ctx->d_wpart, sizeof(double) * need));
-                ctx->wpart_cap = need;
-            }
-            ctx->wstride = R + 2;
-        }
+    if (L.wfuse) ctx->wpart_cap = (size_t)ninst * L.wstride;
+    HIPCHK(h2d(ctx->d_inst, ctx->inst.data(), sizeof(InstDev) * ninst, nullptr, true));
+    InstDev** sorted[3] = {&ctx->d_inst_sorted, &ctx->d_inst_sorted_c, &ctx->d_inst_sorted_v};
+    for (int lay = 0; lay < 3; lay++) {
+        const GramOrder& o = L.order[lay];
+        // one upload of the instance array serves a launch order equal to it (a 65,536-point
+        // grid batch moved ~10 MB of InstDev per order from pageable memory, ~1 ms each)
+        ctx->sorted_alias[lay] = o.ident;
+        if (o.ident) *sorted[lay] = ctx->d_inst;
+        if (o.ident || o.order.empty()) continue;
+        std::vector<InstDev> s;
+        s.reserve(o.order.size());
+        for (int k : o.order) s.push_back(ctx->inst[k]);
+        HIPCHK(h2d(*sorted[lay], s.data(), sizeof(InstDev) * s.size(), nullptr, true));
     }
-
-    HIPCHK(cmalloc((void**)&ctx->d_tables, sizeof(double) * toff));
-    if (tables) HIPCHK(h2d(ctx->d_tables, tables, sizeof(double) * toff, nullptr, true));
-    HIPCHK(cmalloc((void**)&ctx->d_phhi, sizeof(double) * roff));
-    HIPCHK(cmalloc((void**)&ctx->d_phlo, sizeof(double) * roff));
-    HIPCHK(cmalloc((void**)&ctx->d_ftay, sizeof(double) * roff));
-    HIPCHK(cmalloc((void**)&ctx->d_delay, sizeof(double) * roff));
-    {
-        bool sw = false;
-        for (int pi : ctx->upsr) sw = sw || ctx->psrs[pi].spec.o_NE_SW >= 0;
-        if (sw) HIPCHK(cmalloc((void**)&ctx->d_swg, sizeof(double) * roff));
-    }
-    HIPCHK(cmalloc((void**)&ctx->d_M, sizeof(double) * (moff > 0 ? moff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_rt, sizeof(double) * out));
-    HIPCHK(cmalloc((void**)&ctx->d_rp, sizeof(double) * out));
-    HIPCHK(cmalloc((void**)&ctx->d_chi2, sizeof(double) * ninst));
-    HIPCHK(cmalloc((void**)&ctx->d_istatus, sizeof(int) * ninst));
-    HIPCHK(cmalloc((void**)&ctx->d_rscr, sizeof(double) * RSCR * (size_t)ninst));
-    HIPCHK(hipMemsetAsync(ctx->d_istatus, 0, sizeof(int) * ninst, ctx->stream));
-    for (int sl = 0; sl < pint_ctx::NSLOT; sl++) HIPCHK(cmalloc((void**)&ctx->d_chi2g_s[sl], sizeof(double) * ninst));
-    HIPCHK(cmalloc((void**)&ctx->d_lognorm, sizeof(double) * ninst));
-    for (int sl = 0; sl < pint_ctx::NSLOT; sl++) HIPCHK(cmalloc((void**)&ctx->d_chi2lin_s[sl], sizeof(double) * ninst));
-    HIPCHK(cmalloc((void**)&ctx->d_G, sizeof(double) * goff));
-    HIPCHK(cmalloc((void**)&ctx->d_colsq, sizeof(double) * coff * nsplit));
-    HIPCHK(cmalloc((void**)&ctx->d_work, sizeof(double) * soff));
-    for (int sl = 0; sl < pint_ctx::NSLOT; sl++)
-        HIPCHK(cmalloc((void**)&ctx->d_cov_s[sl], sizeof(double) * (cvoff > 0 ? cvoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_sigL, sizeof(double) * soff));
-    for (int sl = 0; sl < pint_ctx::NSLOT; sl++) {
-        HIPCHK(cmalloc((void**)&ctx->d_dpars_s[sl], sizeof(double) * coff));
-        HIPCHK(cmalloc((void**)&ctx->d_errs_s[sl], sizeof(double) * coff));
-        // the per-instance slot past the last column (K+1 stride) is never written by a solve
-        HIPCHK(hipMemsetAsync(ctx->d_dpars_s[sl], 0, sizeof(double) * coff, ctx->stream));
-        HIPCHK(hipMemsetAsync(ctx->d_errs_s[sl], 0, sizeof(double) * coff, ctx->stream));
-    }
+    HIPCHK(h2d(ctx->d_blk_inst, L.blk_inst.data(), sizeof(int) * L.blk_inst.size(), nullptr, true));
+    HIPCHK(h2d(ctx->d_blk_row0, L.blk_row0.data(), sizeof(int) * L.blk_row0.size(), nullptr, true));
+    if (!L.rblk_inst.empty())
+        HIPCHK(h2d(ctx->d_rblk_inst, L.rblk_inst.data(), sizeof(int) * L.rblk_inst.size(), nullptr, true));
+    if (tables) HIPCHK(h2d(ctx->d_tables, tables, sizeof(double) * ctx->tot_table, nullptr, true));
     ctx->out_slot = -1;
     select_out_slot(ctx, ctx->slot);
-    HIPCHK(cmalloc((void**)&ctx->d_lam, sizeof(double) * ninst));
-    HIPCHK(cmalloc((void**)&ctx->d_norms, sizeof(double) * coff));
-    HIPCHK(cmalloc((void**)&ctx->d_ones, sizeof(double) * coff));
-    HIPCHK(cmalloc((void**)&ctx->d_esum, sizeof(double) * (eoff > 0 ? eoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_eD, sizeof(double) * (epoff > 0 ? epoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_eW, sizeof(double) * (epoff > 0 ? epoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_eC, sizeof(double) * (epoff > 0 ? epoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_ecs, sizeof(double) * (epoff > 0 ? epoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_ic, sizeof(InstConst) * ninst));
-    HIPCHK(cmalloc((void**)&ctx->d_dmxv, sizeof(double) * (out > 0 ? out : 1)));
-    {
-        bool any_dmn = false;
-        for (int k = 0; k < ninst; k++) any_dmn |= ctx->psrs[ctx->inst[k].psr].spec.dmn0 < ctx->psrs[ctx->inst[k].psr].spec.nred;
-        HIPCHK(cmalloc((void**)&ctx->d_dfac, sizeof(double) * (any_dmn && out > 0 ? out : 1)));
-    }
-    HIPCHK(cmalloc((void**)&ctx->d_Sd, sizeof(double) * (sdoff > 0 ? sdoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_DD, sizeof(double) * (ddoff > 0 ? ddoff : 1)));
-    HIPCHK(cmalloc((void**)&ctx->d_DCS, sizeof(double) * (ddoff > 0 ? ddoff : 1)));
-    HIPCHK(hipMemsetAsync(ctx->d_cov, 0, sizeof(double) * (cvoff > 0 ? cvoff : 1), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_cov, 0, sizeof(double) * std::max<long>(1, ctx->tot_cv), ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
+}
+
+// pint_set_instances / the batch of a grid: plan, refuse (the context untouched: the resident
+// batch stays usable) or commit.
+static int set_instances_impl(pint_ctx* ctx, int ninst, const int32_t* inst_psr, const double* tables) {
+    if (!ctx || ninst <= 0) return PINT_E_INVALID;
+    BatchLayout L = plan_batch(ctx, ninst, inst_psr, ctx->ncu);
+    if (L.err) {
+        ctx->err = L.err;
+        return PINT_E_INVALID;
+    }
+    return commit_batch(ctx, L, tables);
 }
 
 static int flush_restore(pint_ctx* ctx);

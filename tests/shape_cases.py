@@ -5,7 +5,10 @@ red-noise modes; model_of builds the model from simulation.pta_par by restrictin
 and adding fitted WaveX amplitudes at half-integer multiples of 1 / Tspan above the red-noise
 band (not degenerate with the red-noise basis at the integer multiples); predict_plan repeats
 the dispatch arithmetic of pint_set_instances / pint_fit_step (pint_hip.hip) for a batch of
-that one pulsar and returns the plan Session.last_plan() must report.
+that one pulsar and returns the plan Session.last_plan() must report: of the batch's planner
+plan_batch, the PINT_NSPLIT cap of choose_nsplit, vg_ok, slots_ok / first_ntr, vb_rows_ok and
+plan_vgram (vgram_layout here) and gram_order's launch keys (gram_T, the k_gram_v key); of
+the step's, fit_shape and plan_fit_step.
 
 The wideband sweep (wb_cases.py, test_wideband_sweep.py) uses the same Case with its wideband
 fields set: free DM Taylor terms, DMJUMPs and NE_SW beside the ntim timing columns (ndense),
