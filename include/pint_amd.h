@@ -668,6 +668,19 @@ int pint_graph_launch(pint_ctx *ctx);
 #define PINT_RESID_R2_256 32    /* k_resid2<256> */
 #define PINT_RESID_TILES 64     /* k_resid2 formed the Woodbury trig tiles */
 #define PINT_RESID_DEFERRED 128 /* second half left to k_gram_v (or to the first reader of the residuals) */
+#define PINT_QUERY_EVAL_PATH 8  /* PINT_EVALP_* bits: what the last pint_eval launched before its residual pass */
+#define PINT_EVALP_PREP 1           /* k_prep formed the per-instance constants */
+#define PINT_EVALP_PREP_LANES 2     /* k_prep_lanes did (a batch of small tables) */
+#define PINT_EVALP_PREP_RESTORE 4   /* ... and whichever ran copied the pint_save_tables snapshot back first */
+#define PINT_EVALP_SNAPSHOT 8       /* the evaluation read the snapshot and its constants and wrote them back
+                                       (pint_restore_tables without a k_prep launch) */
+#define PINT_EVALP_SW_GEOM 16       /* k_sw_geom (a solar-wind model in the batch) */
+#define PINT_EVALP_SPIN 32          /* a spin-only grid's shared head and spin part instead of the block launches */
+#define PINT_EVALP_MERGED 64        /* one launch for the isolated, ELL1 and DD blocks (k_eval_mix) */
+#define PINT_EVALP_MERGED_BUDGET 128 /* ... at a fixed register budget (k_eval_mix_w) */
+#define PINT_EVALP_KIND_BUDGET 256  /* some block kind's own launch ran a build at a fixed register budget */
+#define PINT_QUERY_EVAL_KINDS 9 /* bit t set: block kind t (PINT_BIN_*, PINT_BLK_FB_*; PINT_NBLK bits) got a launch
+                                   of its own in the last pint_eval */
 int pint_query(pint_ctx *ctx, int key);
 /* The launch plan of the last pint_fit_step (host bookkeeping, no reference counterpart): which
  * kernel instantiations the call enqueued, as the dispatcher chose them from the batch's padded

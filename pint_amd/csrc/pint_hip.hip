@@ -1224,7 +1224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) voi
     eval_mix_body<WANT_M>(PINT_EVAL_MIX_PASS);
 }
 // the k_eval build of every block kind at the compiler's own register allocation, [with M][kind]
-// (the builds at a register budget are pint_eval's special cases)
+// (the builds at a register budget: eval_kind_kernel, beside pint_eval's plan)
 using EvalKernel = decltype(&k_eval<0, 0>);
 using EvalMixKernel = decltype(&k_eval_mix<0>);
 template <int WM, size_t... BT>
@@ -6799,7 +6799,7 @@ struct PsrHost {
 };
 
 // pint_ctx::post: some instance of the batch has the component, so its pass follows the
-// evaluation (the order of the launches: pint_eval)
+// evaluation (the order of the launches: launch_post_passes)
 enum : unsigned {
     POST_WAVEX = 1,        // WaveX / DMWaveX, or chromatic terms: k_wavex
     POST_CHROM = 2,        // ChromaticCM / CMWaveX: k_wavex<true> instead of the plain build (POST_WAVEX is set too)
@@ -6844,6 +6844,8 @@ struct pint_ctx {
     int fuse_r2 = 1;     // PINT_FUSE_R2: the fit layout's k_resid2 folded into k_gram_v's staging
     bool r2_pending = false;  // k_resid2 of the last pass deferred (the Gram formed its residuals)
     int resid_path = 0;  // PINT_RESID_* of the last pint_eval's residual pass (PINT_QUERY_RESID_PATH)
+    int eval_path = 0;   // PINT_EVALP_* of the last pint_eval (PINT_QUERY_EVAL_PATH)
+    int eval_kinds = 0;  // ... and the block kinds that got a launch of their own (PINT_QUERY_EVAL_KINDS)
     bool grid_valid = false;  // the batch is pint_set_grid's: grid_psr's points, options grid_opts
     std::vector<double> grid_spec_host;  // pint_set_grid's spec, kept while its upload may run
     int grid_psr = -1;
@@ -9149,16 +9151,18 @@ static int decode_status(pint_ctx* ctx, int st) {
     return PINT_OK;
 }
 
-// Evaluate phases/delays (+ design matrix) and residuals for every instance.
-// k_prep / k_apply, or their lane-per-instance forms for a batch of small tables
+// k_prep / k_apply, or their lane-per-instance forms for a batch of small tables; the launch
+// shape of either form
 static bool prep_lanes(const pint_ctx* ctx) { return ctx->prep_lanes && ctx->max_ts <= PREP_LANE_TAB; }
-static void launch_prep(pint_ctx* ctx, double* tables, const double* tables0, InstConst* ic) {
-    if (prep_lanes(ctx))
-        hipLaunchKernelGGL(k_prep_lanes, dim3((ctx->ninst + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_psrs,
+static dim3 prep_grid(const pint_ctx* ctx, bool lanes) { return dim3(lanes ? (ctx->ninst + 63) / 64 : ctx->ninst); }
+static dim3 prep_block(bool lanes) { return dim3(lanes ? 64 : PREP_T); }
+static void launch_prep(pint_ctx* ctx, bool lanes, double* tables, const double* tables0, InstConst* ic) {
+    if (lanes)
+        hipLaunchKernelGGL(k_prep_lanes, prep_grid(ctx, lanes), prep_block(lanes), 0, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, ctx->ninst, tables, tables0, ic);
     else
-        hipLaunchKernelGGL(k_prep, dim3(ctx->ninst), dim3(PREP_T), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, tables,
-                           tables0, ic);
+        hipLaunchKernelGGL(k_prep, prep_grid(ctx, lanes), prep_block(lanes), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
+                           tables, tables0, ic);
 }
 // The wideband DM kernels read the per-instance constants only for a solar-wind model (the
 // pulsar direction of its geometry): form them here if the tables changed since the last
@@ -9168,231 +9172,388 @@ static int ensure_ic_solar_wind(pint_ctx* ctx) {
     bool sw = false;
     for (int pi : ctx->upsr) sw = sw || (ctx->psrs[pi].dev.wb && ctx->psrs[pi].spec.o_NE_SW >= 0);
     if (!sw) return PINT_OK;
-    launch_prep(ctx, ctx->d_tables, nullptr, ctx->d_ic);
+    launch_prep(ctx, prep_lanes(ctx), ctx->d_tables, nullptr, ctx->d_ic);
     HIPCHK(hipGetLastError());
     ctx->ic_valid = true;
     return PINT_OK;
 }
 static void launch_apply(pint_ctx* ctx, const double* lam, double lam_u) {
+    const bool lanes = prep_lanes(ctx);
     ctx->tables_fresh = false;
-    if (prep_lanes(ctx))
-        hipLaunchKernelGGL(k_apply_lanes, dim3((ctx->ninst + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_psrs,
+    if (lanes)
+        hipLaunchKernelGGL(k_apply_lanes, prep_grid(ctx, lanes), prep_block(lanes), 0, ctx->stream, ctx->d_psrs,
                            ctx->d_inst, ctx->ninst, ctx->d_tables, ctx->d_dpars, lam, ctx->d_ic, lam_u);
     else
-        hipLaunchKernelGGL(k_apply, dim3(ctx->ninst), dim3(PREP_T), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
+        hipLaunchKernelGGL(k_apply, prep_grid(ctx, lanes), prep_block(lanes), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
                            ctx->d_tables, ctx->d_dpars, lam, ctx->d_ic, lam_u);
 }
+// the tables hold a step applied on the device, which formed their constants too (k_apply, or
+// the solve's apply tail): the phases of the last evaluation are no longer theirs
+static void tables_applied(pint_ctx* ctx) {
+    ctx->ic_valid = true;
+    ctx->phases_valid = false;
+}
 
-// k_resid2 of the last residual pass (with wt, the Woodbury trig tiles)
-static void launch_resid2(pint_ctx* ctx, bool wt) {
-    const size_t wlds = wt ? sizeof(double) * std::max((RES_BT / 64) * 32 * WT_CS2, 4 * 256) : 0;
-    const double* ep = ctx->efz ? ctx->d_epart : nullptr;
-    if (wt) ctx->resid_path |= PINT_RESID_TILES;
-    if (!ctx->efz && ctx->small && ctx->maxn <= RES_SMALLN) {
-        ctx->resid_path |= PINT_RESID_R2_64;
-        hipLaunchKernelGGL(k_resid2<64>, dim3((ctx->nrblk + 3) / 4), dim3(RES_BT), wlds, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_ftay, ctx->d_rt, ctx->d_rp, ctx->d_rpart,
-                           wt ? ctx->d_wtile : nullptr, ep);
-    } else {
-        ctx->resid_path |= PINT_RESID_R2_256;
-        hipLaunchKernelGGL(k_resid2<RES_BT>, dim3(ctx->nrblk), dim3(RES_BT), wlds, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_ftay, ctx->d_rt, ctx->d_rp, ctx->d_rpart,
-                           wt ? ctx->d_wtile : nullptr, ep);
-    }
+// ---- the residual pass's second half: one choice for pint_eval's plan and for flush_r2 ----
+// a batch of small instances off the fused first half: a wave per residual block (k_resid12,
+// k_resid1<64>, k_resid2<64>)
+// (256-row blocks for small batches were measured: resid1 faster, resid2 and k_wsolve's
+// longer tile sums slower, the step ~1.4 us slower at 9 pulsars)
+static bool resid_small(const pint_ctx* ctx) { return !ctx->efz && ctx->small && ctx->maxn <= RES_SMALLN; }
+
+using Resid2Kernel = decltype(&k_resid2<64>);
+struct Resid2Plan {
+    Resid2Kernel kern;
+    int grid;
+    bool tiles;  // the Woodbury trig tiles
+    size_t lds;  // ... their dynamic LDS
+    int mask;    // PINT_RESID_R2_64 or _R2_256, and PINT_RESID_TILES
+};
+// k_resid2 of a residual pass (with wt, the Woodbury trig tiles)
+static Resid2Plan plan_resid2(const pint_ctx* ctx, bool wt) {
+    Resid2Plan r{};
+    if (resid_small(ctx)) r.kern = k_resid2<64>, r.grid = (ctx->nrblk + 3) / 4, r.mask = PINT_RESID_R2_64;
+    else r.kern = k_resid2<RES_BT>, r.grid = ctx->nrblk, r.mask = PINT_RESID_R2_256;
+    r.tiles = wt;
+    r.lds = wt ? sizeof(double) * std::max((RES_BT / 64) * 32 * WT_CS2, 4 * 256) : 0;
+    if (wt) r.mask |= PINT_RESID_TILES;
+    return r;
+}
+static void launch_resid2(pint_ctx* ctx, const Resid2Plan& r) {
+    hipLaunchKernelGGL(r.kern, dim3(r.grid), dim3(RES_BT), r.lds, ctx->stream, ctx->d_psrs, ctx->d_inst,
+                       ctx->d_rblk_inst, ctx->nrblk, ctx->d_ftay, ctx->d_rt, ctx->d_rp, ctx->d_rpart,
+                       r.tiles ? ctx->d_wtile : nullptr, ctx->efz ? ctx->d_epart : nullptr);
 }
 
 // The fit layout's residual pass may leave k_resid2 to the Gram (GvResid) when every instance
 // takes k_gram_v and nothing else of the fit step reads the time residuals: no ECORR epochs
 // (k_ecorr), no wideband rows (k_wb_gram), and <= 64 residual blocks per instance (the mean
 // summed on one wave as k_resid2 sums it).  PINT_FUSE_R2=0 keeps k_resid2 in the pass.
-static bool can_defer_r2(const pint_ctx* ctx) {
-    return ctx->fuse_r2 && ctx->m_compact && ctx->n_vg == ctx->ninst && ctx->max_nep == 0 && !ctx->wbfit &&
+// compact: the design matrix's layout (pint_eval's plan asks before it commits m_compact).
+static bool can_defer_r2(const pint_ctx* ctx, bool compact) {
+    return ctx->fuse_r2 && compact && ctx->n_vg == ctx->ninst && ctx->max_nep == 0 && !ctx->wbfit &&
            ctx->maxn <= 64 * (ctx->efz ? EF_ROWS : RES_RB);
 }
 
-// a reader of the time/phase residuals or their chi2 partials after a deferred pass
+// a reader of the time/phase residuals or their chi2 partials after a deferred pass: the second
+// half as the context stands now
 static void flush_r2(pint_ctx* ctx) {
     if (!ctx->r2_pending) return;
     ctx->r2_pending = false;
-    launch_resid2(ctx, false);
+    const Resid2Plan r = plan_resid2(ctx, false);
+    ctx->resid_path |= r.mask;
+    launch_resid2(ctx, r);
 }
 
 // the grid of a row pass (k_sw_geom and the passes after the evaluation): instances x 256-row
 // blocks of the longest instance's n + 1 rows
 static dim3 pass_grid(const pint_ctx* ctx, int ninst) { return dim3(ninst, (ctx->maxn + 256) / 256); }
 
-int pint_eval(pint_ctx* ctx, int want_M) {
-    if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
-    hipSetDevice(ctx->device);
-    if (want_M < 0 || want_M > 2) return PINT_E_INVALID;
-    ctx->r2_pending = false;  // (this pass replaces the residuals a deferred k_resid2 would form)
-    ctx->resid_path = 0;
-    if (want_M) ctx->m_compact = (want_M == 2) ? 1 : 0;
-    // the full and compact layouts place the red-noise columns differently; each is written
-    // once after pint_set_instances (M is reallocated there)
-    int write_red = 0;
-    if (want_M) {
-        write_red = ctx->red_valid[want_M == 2] ? 0 : 1;
-        ctx->red_valid[want_M == 2] = 1;
-        ctx->red_valid[want_M != 2] = 0;  // the other layout's red columns get overwritten
-        if (ctx->dm_noise_pend) {  // the evaluation with M rewrites the DM-noise scale d_dfac
-            if (int rc = flush_cq_now(ctx)) return rc;
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied, 0));
-            ctx->dm_noise_pend = false;
-        }
-    }
-    record(ctx, want_M ? 2 : 0);
-    ctx->phases_valid = true;  // (enqueued below, on the stream the photon passes run on)
-    const double* tabs = ctx->d_tables;
-    const InstConst* icp = ctx->d_ic;
-    EvalRestore rs{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!ctx->ic_valid) {  // (k_apply refreshes them itself)
-        if (ctx->restore_pending && ctx->ic0_valid) {
-            // restore: the evaluation reads the snapshot and its constants (pint_save_tables) and
-            // each instance's first block writes them back -- no k_prep launch in a refit step
-            tabs = ctx->d_tables0;
-            icp = ctx->d_ic0;
-            rs.tables = ctx->d_tables;
-            rs.ic = ctx->d_ic;
-        } else {
-            launch_prep(ctx, ctx->d_tables, ctx->restore_pending ? (const double*)ctx->d_tables0 : nullptr, ctx->d_ic);
-            HIPCHK(hipGetLastError());
-        }
-        ctx->restore_pending = false;
-        ctx->ic_valid = true;
-    }
-    if (ctx->efz && ctx->nrblk > 0) {  // the residual pass's first half in the evaluation's blocks
-        rs.rph = ctx->d_rp;
-        rs.epart = ctx->d_epart;
-    }
-    // a spin-only grid's first evaluation with the design matrix: the shared head, then each
-    // point's spin part
-    const bool spin_pass = want_M && ctx->spin_grid && ctx->tables_fresh && ctx->spin_eval && rs.tables == nullptr &&
-                           !ctx->efz && ctx->d_shr && ctx->blk_off[PINT_NBLK] == ctx->blk_off[1];
-    if (ctx->d_swg) {  // SolarWindDispersion: the rows' geometry at these constants, read by the evaluation
-        // (the shared head reads the first point's rows only)
-        hipLaunchKernelGGL(k_sw_geom, pass_grid(ctx, spin_pass ? 1 : ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs,
-                           ctx->d_inst, icp, ctx->d_swg);
-        HIPCHK(hipGetLastError());
-        rs.swg = ctx->d_swg;
-    }
-    if (spin_pass) {
-        const int n1 = ctx->inst[0].n + 1;
-        hipLaunchKernelGGL(k_eval_head, dim3((n1 + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                           tabs, icp, rs.swg, ctx->d_shr);
-        hipLaunchKernelGGL(k_eval_spin, dim3((ctx->ninst + 3) / 4), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                           ctx->ninst, tabs, icp, ctx->d_shr, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay,
-                           ctx->d_M);
-        HIPCHK(hipGetLastError());
-        ctx->n_spin_eval++;
-    }
-    // a batch of one model (a grid's points, an all-isolated PTA) takes that model's own
-    // build, whose register set the other models do not raise (k_eval<WM, 0>: 48 instead
-    // of 84 VGPRs + spills with M for an isolated pulsar); PINT_EVAL_MERGE bit 2 merges anyway
+// ---- pint_eval: the plan ----
+// where the evaluation's tables and per-instance constants come from
+enum EvalSource {
+    EVAL_SRC_CURRENT,       // the constants are current (k_apply refreshes them itself): no launch
+    EVAL_SRC_PREP,          // k_prep forms them from the tables
+    EVAL_SRC_PREP_RESTORE,  // ... and copies the snapshot back first (a restore without snapshot constants)
+    EVAL_SRC_SNAPSHOT       // the evaluation reads the snapshot and its constants (pint_save_tables) and each
+                            // instance's first block writes them back -- no k_prep launch in a refit step
+};
+enum EvalResid1 { RESID1_NONE, RESID1_EFUSED, RESID1_R12, RESID1_64, RESID1_256 };  // NONE: no residual rows
+enum EvalResid2 { RESID2_NONE, RESID2_LAUNCH, RESID2_DEFERRED };
+
+using PostWavexKernel = decltype(&k_wavex<true>);
+
+// What one pint_eval(want_M) launches and what it leaves in the context (commit_eval).
+struct EvalPlan {
+    // layout
+    int want_M;
+    int compact;       // the design matrix in the fit layout (want_M == 2)
+    int write_red;     // ... with its red-noise columns, not yet written in this layout
+    bool wait_copy;    // a copy-stream PLDMNoise realisation still reads d_dfac, which this evaluation rewrites
+    // tables and constants
+    EvalSource source;
+    bool prep_lanes;   // k_prep_lanes instead of k_prep
+    // launches, in stream order
+    int sw_ninst;      // k_sw_geom over this many instances (0: no solar wind in the batch)
+    bool spin_pass;    // k_eval_head + k_eval_spin instead of the block launches
+    EvalMixKernel mix;             // the merged launch of kinds 0..2 (null: none)
+    EvalKernel kind[PINT_NBLK];    // the launch of a block kind's own (null: empty, merged, or the spin pass)
+    unsigned post;                 // POST_*
+    PostWavexKernel wavex;
+    EvalResid1 resid1;
+    EvalResid2 resid2;
+    Resid2Plan r2;                 // with RESID2_LAUNCH
+    bool tiles;                    // the pass forms the Woodbury dots' tiles (wtile_valid)
+    // as the queries report them
+    int resid_mask, eval_path, eval_kinds;
+};
+
+// a batch of one model (a grid's points, an all-isolated PTA) takes that model's own
+// build, whose register set the other models do not raise (k_eval<WM, 0>: 48 instead
+// of 84 VGPRs + spills with M for an isolated pulsar); PINT_EVAL_MERGE bit 2 merges anyway
+static bool eval_merged(const pint_ctx* ctx, int want_M) {
     int ntyp = 0;
     for (int t = 0; t < 3; t++) ntyp += ctx->blk_off[t + 1] > ctx->blk_off[t];
-    const bool mix = ((ctx->eval_merge >> (want_M ? 1 : 0)) & 1) && (ntyp > 1 || (ctx->eval_merge & 4));
-    if (!spin_pass && mix && ctx->nblk > 0) {
-        // the 3-waves/SIMD register budget (spills) pays when the blocks fill the SIMDs more
-        // than twice; a small batch (<= 2 waves per SIMD) runs the unconstrained build (203
-        // VGPRs, no spills) at its own occupancy
-        const bool small = ctx->nblk <= 2 * 256;
-        EvalMixKernel kern = want_M ? k_eval_mix<1> : k_eval_mix<0>;
-        if (want_M && ctx->eval_wpe == 3 && !small) kern = k_eval_mix_w<1, 3>;
-        else if (want_M && ctx->eval_wpe == 4) kern = k_eval_mix_w<1, 4>;
-        hipLaunchKernelGGL(kern, dim3(ctx->nblk), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_blk_inst,
-                           ctx->d_blk_row0, ctx->blk_off[1], ctx->blk_off[2], ctx->blk_off[3], tabs, icp, ctx->d_phhi,
-                           ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, ctx->d_dmxv, want_M == 2 ? 1 : 0, write_red,
-                           ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs);
-        HIPCHK(hipGetLastError());
-    }
+    return ((ctx->eval_merge >> (want_M ? 1 : 0)) & 1) && (ntyp > 1 || (ctx->eval_merge & 4));
+}
+// the merged launch's build
+static EvalMixKernel eval_mix_kernel(const pint_ctx* ctx, int want_M) {
+    // the 3-waves/SIMD register budget (spills) pays when the blocks fill the SIMDs more
+    // than twice; a small batch (<= 2 waves per SIMD) runs the unconstrained build (203
+    // VGPRs, no spills) at its own occupancy
+    const bool small = ctx->nblk <= 2 * 256;
+    EvalMixKernel kern = want_M ? k_eval_mix<1> : k_eval_mix<0>;
+    if (want_M && ctx->eval_wpe == 3 && !small) kern = k_eval_mix_w<1, 3>;
+    else if (want_M && ctx->eval_wpe == 4) kern = k_eval_mix_w<1, 4>;
+    return kern;
+}
+// the build of block kind t's own launch over nb blocks: EVAL_KERNELS' unless a register budget
+// was measured to win
+static EvalKernel eval_kind_kernel(const pint_ctx* ctx, int want_M, int t, int nb) {
+    // the isolated build at a register budget of 6 waves/SIMD with M (80 VGPRs, no spills:
+    // 0.28 vs 0.31 ms on the 65,536-point NGC6440E grid) and 8 without (64 VGPRs, 36 B of
+    // spills: 0.143 vs 0.162 ms); 8 with M spilled 76 B and lost (0.35 ms).
+    // PINT_EVAL0_WPE=0: the compiler's own allocation (84 / 74 VGPRs, 5 / 6 waves)
+    if (t == 0 && ctx->eval0_wpe) return want_M ? k_eval<1, 0, 6> : k_eval<0, 0, 8>;
+    // a large one-model ELL1 or DD batch (a J0740 grid) with M at the merged build's
+    // budget of 3 waves/SIMD (168 VGPRs + spills) instead of 2 (174 / 202 VGPRs)
+    if (want_M && (t == 1 || t == 2) && ctx->evalb_wpe == 3 && nb > 2 * 256)
+        return t == 1 ? k_eval<1, 1, 3> : k_eval<1, 2, 3>;
+    return EVAL_KERNELS[want_M != 0][t];
+}
+
+// The plan of pint_eval(want_M) on the context as it stands: host arithmetic only, no HIP call,
+// nothing written.  Every decision is made here, once.
+static EvalPlan plan_eval(const pint_ctx* ctx, int want_M) {
+    EvalPlan p{};
+    p.want_M = want_M;
+    p.compact = want_M == 2;
+    // the full and compact layouts place the red-noise columns differently; each is written
+    // once after pint_set_instances (M is reallocated there)
+    p.write_red = want_M && !ctx->red_valid[p.compact];
+    p.wait_copy = want_M && ctx->dm_noise_pend;  // the evaluation with M rewrites the DM-noise scale d_dfac
+    if (ctx->ic_valid) p.source = EVAL_SRC_CURRENT;
+    else if (!ctx->restore_pending) p.source = EVAL_SRC_PREP;
+    else p.source = ctx->ic0_valid ? EVAL_SRC_SNAPSHOT : EVAL_SRC_PREP_RESTORE;
+    p.prep_lanes = prep_lanes(ctx);
+    const bool prep = p.source == EVAL_SRC_PREP || p.source == EVAL_SRC_PREP_RESTORE;
+    if (prep) p.eval_path |= p.prep_lanes ? PINT_EVALP_PREP_LANES : PINT_EVALP_PREP;
+    if (p.source == EVAL_SRC_PREP_RESTORE) p.eval_path |= PINT_EVALP_PREP_RESTORE;
+    if (p.source == EVAL_SRC_SNAPSHOT) p.eval_path |= PINT_EVALP_SNAPSHOT;
+    // a spin-only grid's first evaluation with the design matrix: the shared head, then each
+    // point's spin part.  Neither reads the snapshot or writes it back, and neither carries the
+    // residual pass's first half: the snapshot source and the fused first half exclude it
+    p.spin_pass = want_M && ctx->spin_grid && ctx->tables_fresh && ctx->spin_eval && p.source != EVAL_SRC_SNAPSHOT &&
+                  !ctx->efz && ctx->d_shr && ctx->blk_off[PINT_NBLK] == ctx->blk_off[1];
+    if (p.spin_pass) p.eval_path |= PINT_EVALP_SPIN;
+    // SolarWindDispersion: the rows' geometry at these constants, read by the evaluation
+    // (the shared head reads the first point's rows only)
+    p.sw_ninst = !ctx->d_swg ? 0 : (p.spin_pass ? 1 : ctx->ninst);
+    if (p.sw_ninst) p.eval_path |= PINT_EVALP_SW_GEOM;
     // one launch per binary model, back to back on the stream: all models without the merged
     // launch; ELL1H/BT/DDK/DDS/DDH/ELL1k and the FBn orbits' block kinds always (they stay out of
     // k_eval_mix so its register set, which every block of the merged launch carries, is not raised
     // by the rarer models)
-    for (int t = spin_pass ? PINT_NBLK : (mix ? 3 : 0); t < PINT_NBLK; t++) {
-        int nb = ctx->blk_off[t + 1] - ctx->blk_off[t];
-        if (nb == 0) continue;
-        const int* bi = ctx->d_blk_inst + ctx->blk_off[t];
-        const int* br = ctx->d_blk_row0 + ctx->blk_off[t];
-        EvalKernel kern = EVAL_KERNELS[want_M != 0][t];
-        // the isolated build at a register budget of 6 waves/SIMD with M (80 VGPRs, no spills:
-        // 0.28 vs 0.31 ms on the 65,536-point NGC6440E grid) and 8 without (64 VGPRs, 36 B of
-        // spills: 0.143 vs 0.162 ms); 8 with M spilled 76 B and lost (0.35 ms).
-        // PINT_EVAL0_WPE=0: the compiler's own allocation (84 / 74 VGPRs, 5 / 6 waves)
-        if (t == 0 && ctx->eval0_wpe) {
-            kern = want_M ? k_eval<1, 0, 6> : k_eval<0, 0, 8>;
-        } else if (want_M && (t == 1 || t == 2) && ctx->evalb_wpe == 3 && nb > 2 * 256) {
-            // a large one-model ELL1 or DD batch (a J0740 grid) with M at the merged build's
-            // budget of 3 waves/SIMD (168 VGPRs + spills) instead of 2 (174 / 202 VGPRs)
-            kern = t == 1 ? k_eval<1, 1, 3> : k_eval<1, 2, 3>;
-        }
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, bi, br, tabs, icp,
-                           ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, ctx->d_dmxv,
-                           want_M == 2 ? 1 : 0, write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, rs);
-        HIPCHK(hipGetLastError());
+    const bool merged = !p.spin_pass && eval_merged(ctx, want_M);
+    if (merged && ctx->nblk > 0) {
+        p.mix = eval_mix_kernel(ctx, want_M);
+        p.eval_path |= PINT_EVALP_MERGED;
+        if (p.mix != (want_M ? k_eval_mix<1> : k_eval_mix<0>)) p.eval_path |= PINT_EVALP_MERGED_BUDGET;
     }
-    // the passes after the evaluation, in their fixed order (the contract above k_sw_geom), each
-    // only for a batch that has its component: one launch on the rows' grid, the shared leading
-    // arguments, then the pass's own (the status words of the passes that bound the added delay)
-#define PINT_PASS(kern, ...)                                                                                       \
-    do {                                                                                                           \
-        hipLaunchKernelGGL(kern, pass_grid(ctx, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, \
-                           tabs, icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, want_M ? ctx->d_M : nullptr,         \
-                           want_M == 2, ##__VA_ARGS__);                                                            \
-        HIPCHK(hipGetLastError());                                                                                 \
-    } while (0)
+    for (int t = merged ? 3 : 0; t < PINT_NBLK && !p.spin_pass; t++) {
+        const int nb = ctx->blk_off[t + 1] - ctx->blk_off[t];
+        if (nb == 0) continue;
+        p.kind[t] = eval_kind_kernel(ctx, want_M, t, nb);
+        p.eval_kinds |= 1 << t;
+        if (p.kind[t] != EVAL_KERNELS[want_M != 0][t]) p.eval_path |= PINT_EVALP_KIND_BUDGET;
+    }
+    // the passes after the evaluation
     // (a batch with chromatic terms takes the chromatic build; every other batch the plain one)
-    const auto kw = ctx->post & POST_CHROM ? k_wavex<true> : k_wavex<false>;
-    if (ctx->post & POST_WAVEX) PINT_PASS(kw, ctx->d_status, ctx->d_istatus);
-    if (ctx->post & POST_FDJUMP) PINT_PASS(k_fdjump, ctx->d_status, ctx->d_istatus);
-    if (ctx->post & POST_GLITCH) PINT_PASS(k_glitch);
-    if (ctx->post & POST_PHASE_TERMS) PINT_PASS(k_phase_terms);
-#undef PINT_PASS
-    record(ctx, want_M ? 3 : 1);
-    record(ctx, 4);
+    p.post = ctx->post;
+    p.wavex = ctx->post & POST_CHROM ? k_wavex<true> : k_wavex<false>;
     if (ctx->nrblk > 0) {
         // without the design matrix (the post-fit evaluation a GLS chi2 follows): the Woodbury
         // dot products come with the residual pass (k_resid2 tiles, k_rsum)
-        const bool wt = ctx->wfuse && want_M == 0;
-        // (256-row blocks for small batches were measured: resid1 faster, resid2 and k_wsolve's
-        // longer tile sums slower, the step ~1.4 us slower at 9 pulsars)
+        p.tiles = ctx->wfuse && want_M == 0;
         // the fit layout's pass on the k_gram_v path: k_resid1 only, the Gram stages the time
         // residuals itself and k_resid2 waits for a reader of them (flush_r2)
-        const bool defer2 = want_M == 2 && can_defer_r2(ctx);
-        const bool fused12 = !ctx->efz && ctx->small && ctx->maxn <= RES_SMALLN && !wt && !defer2 && ctx->resid12;
-        if (ctx->efz) {
-            // (k_resid1's work done by the evaluation's blocks)
-            ctx->resid_path |= PINT_RESID_EFUSED;
-        } else if (fused12) {  // one wave per instance does both passes
-            ctx->resid_path |= PINT_RESID_R12;
-            hipLaunchKernelGGL(k_resid12, dim3((ctx->nrblk + 3) / 4), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
-                               ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay,
-                               ctx->d_rt, ctx->d_rp, ctx->d_rpart);
-        } else if (ctx->small && ctx->maxn <= RES_SMALLN) {  // a wave per residual block
-            const int nb4 = (ctx->nrblk + 3) / 4;
-            ctx->resid_path |= PINT_RESID_R1_64;
-            hipLaunchKernelGGL(k_resid1<64>, dim3(nb4), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
-                               ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_rp, ctx->d_rpart);
-        } else {
-            ctx->resid_path |= PINT_RESID_R1_256;
-            hipLaunchKernelGGL(k_resid1<RES_BT>, dim3(ctx->nrblk), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
-                               ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_rp,
-                               ctx->d_rpart);
-        }
-        if (defer2) {
-            ctx->r2_pending = true;
-            ctx->resid_path |= PINT_RESID_DEFERRED;
-        } else if (!fused12) launch_resid2(ctx, wt);
+        const bool defer2 = want_M == 2 && can_defer_r2(ctx, p.compact);
+        // one wave per instance does both halves
+        const bool fused12 = resid_small(ctx) && !p.tiles && !defer2 && ctx->resid12;
+        if (ctx->efz) p.resid1 = RESID1_EFUSED, p.resid_mask = PINT_RESID_EFUSED;  // (the evaluation's blocks)
+        else if (fused12) p.resid1 = RESID1_R12, p.resid_mask = PINT_RESID_R12;
+        else if (resid_small(ctx)) p.resid1 = RESID1_64, p.resid_mask = PINT_RESID_R1_64;  // a wave per block
+        else p.resid1 = RESID1_256, p.resid_mask = PINT_RESID_R1_256;
+        p.resid2 = defer2 ? RESID2_DEFERRED : (fused12 ? RESID2_NONE : RESID2_LAUNCH);
+        if (p.resid2 == RESID2_LAUNCH) p.r2 = plan_resid2(ctx, p.tiles), p.resid_mask |= p.r2.mask;
+        if (p.resid2 == RESID2_DEFERRED) p.resid_mask |= PINT_RESID_DEFERRED;
+    }
+    return p;
+}
+
+// Every context field pint_eval sets, from the plan, before its first launch.
+static void commit_eval(pint_ctx* ctx, const EvalPlan& p) {
+    if (p.want_M) {
+        ctx->m_compact = p.compact;
+        ctx->red_valid[p.compact] = 1;
+        ctx->red_valid[!p.compact] = 0;  // the other layout's red columns get overwritten
+    }
+    if (p.wait_copy) ctx->dm_noise_pend = false;
+    ctx->phases_valid = true;  // (enqueued below, on the stream the photon passes run on)
+    if (p.source != EVAL_SRC_CURRENT) {
+        ctx->restore_pending = false;
+        ctx->ic_valid = true;
+    }
+    if (p.spin_pass) ctx->n_spin_eval++;
+    // (this pass replaces the residuals a deferred k_resid2 would form)
+    ctx->r2_pending = p.resid2 == RESID2_DEFERRED;
+    if (p.resid1 != RESID1_NONE) {
         // the chi2 partials are summed when the chi2 is read (pint_read_resids) or by k_wsolve,
         // which needs them anyway: no launch of its own in a fit step
         ctx->chi2_pending = true;
-        ctx->wtile_valid = wt;
+        ctx->wtile_valid = p.tiles;
     }
+    ctx->resid_path = p.resid_mask;
+    ctx->eval_path = p.eval_path;
+    ctx->eval_kinds = p.eval_kinds;
+}
+
+// ---- pint_eval: the launch stages, in stream order ----
+// what every evaluation kernel and post pass reads: the tables, their constants, and the
+// evaluation blocks' side inputs and outputs
+struct EvalArgs {
+    const double* tabs;
+    const InstConst* icp;
+    EvalRestore rs;
+};
+static EvalArgs eval_args(const pint_ctx* ctx, const EvalPlan& p) {
+    EvalArgs a{ctx->d_tables, ctx->d_ic, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+    if (p.source == EVAL_SRC_SNAPSHOT) {
+        a.tabs = ctx->d_tables0;
+        a.icp = ctx->d_ic0;
+        a.rs.tables = ctx->d_tables;
+        a.rs.ic = ctx->d_ic;
+    }
+    if (p.resid1 == RESID1_EFUSED) {  // the residual pass's first half in the evaluation's blocks
+        a.rs.rph = ctx->d_rp;
+        a.rs.epart = ctx->d_epart;
+    }
+    if (p.sw_ninst) a.rs.swg = ctx->d_swg;
+    return a;
+}
+
+static int launch_wait_copy(pint_ctx* ctx, const EvalPlan& p) {
+    if (!p.wait_copy) return PINT_OK;
+    if (int rc = flush_cq_now(ctx)) return rc;
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied, 0));
+    return PINT_OK;
+}
+
+static int launch_source(pint_ctx* ctx, const EvalPlan& p) {
+    if (p.source != EVAL_SRC_PREP && p.source != EVAL_SRC_PREP_RESTORE) return PINT_OK;
+    launch_prep(ctx, p.prep_lanes, ctx->d_tables, p.source == EVAL_SRC_PREP_RESTORE ? (const double*)ctx->d_tables0 : nullptr,
+                ctx->d_ic);
     HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+static int launch_sw_geom(pint_ctx* ctx, const EvalPlan& p, const EvalArgs& a) {
+    if (!p.sw_ninst) return PINT_OK;
+    hipLaunchKernelGGL(k_sw_geom, pass_grid(ctx, p.sw_ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
+                       a.icp, ctx->d_swg);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+static int launch_eval_blocks(pint_ctx* ctx, const EvalPlan& p, const EvalArgs& a) {
+    if (p.spin_pass) {
+        const int n1 = ctx->inst[0].n + 1;
+        hipLaunchKernelGGL(k_eval_head, dim3((n1 + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
+                           a.tabs, a.icp, a.rs.swg, ctx->d_shr);
+        hipLaunchKernelGGL(k_eval_spin, dim3((ctx->ninst + 3) / 4), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst,
+                           ctx->ninst, a.tabs, a.icp, ctx->d_shr, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay,
+                           ctx->d_M);
+        HIPCHK(hipGetLastError());
+    }
+    if (p.mix) {
+        hipLaunchKernelGGL(p.mix, dim3(ctx->nblk), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, ctx->d_blk_inst,
+                           ctx->d_blk_row0, ctx->blk_off[1], ctx->blk_off[2], ctx->blk_off[3], a.tabs, a.icp, ctx->d_phhi,
+                           ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, ctx->d_dmxv, p.compact, p.write_red,
+                           ctx->d_status, ctx->d_istatus, ctx->d_dfac, a.rs);
+        HIPCHK(hipGetLastError());
+    }
+    for (int t = 0; t < PINT_NBLK; t++) {
+        if (!p.kind[t]) continue;
+        hipLaunchKernelGGL(p.kind[t], dim3(ctx->blk_off[t + 1] - ctx->blk_off[t]), dim3(256), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, ctx->d_blk_inst + ctx->blk_off[t], ctx->d_blk_row0 + ctx->blk_off[t], a.tabs, a.icp,
+                           ctx->d_phhi, ctx->d_phlo, ctx->d_ftay, ctx->d_delay, ctx->d_M, ctx->d_dmxv, p.compact,
+                           p.write_red, ctx->d_status, ctx->d_istatus, ctx->d_dfac, a.rs);
+        HIPCHK(hipGetLastError());
+    }
+    return PINT_OK;
+}
+
+}  // extern "C" (launch_post is a template)
+// one pass after the evaluation: a launch on the rows' grid, the shared leading arguments, then
+// the pass's own
+template <typename Kernel, typename... Own>
+static int launch_post(pint_ctx* ctx, const EvalPlan& p, const EvalArgs& a, Kernel kern, Own... own) {
+    hipLaunchKernelGGL(kern, pass_grid(ctx, ctx->ninst), dim3(256), 0, ctx->stream, ctx->d_psrs, ctx->d_inst, a.tabs,
+                       a.icp, ctx->d_delay, ctx->d_phhi, ctx->d_phlo, p.want_M ? ctx->d_M : nullptr, p.want_M == 2, own...);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+extern "C" {
+
+// the passes after the evaluation, in their fixed order (the contract above k_sw_geom), each
+// only for a batch that has its component (with the status words, the passes that bound the
+// added delay)
+static int launch_post_passes(pint_ctx* ctx, const EvalPlan& p, const EvalArgs& a) {
+    int rc = PINT_OK;
+    if (!rc && (p.post & POST_WAVEX)) rc = launch_post(ctx, p, a, p.wavex, ctx->d_status, ctx->d_istatus);
+    if (!rc && (p.post & POST_FDJUMP)) rc = launch_post(ctx, p, a, k_fdjump, ctx->d_status, ctx->d_istatus);
+    if (!rc && (p.post & POST_GLITCH)) rc = launch_post(ctx, p, a, k_glitch);
+    if (!rc && (p.post & POST_PHASE_TERMS)) rc = launch_post(ctx, p, a, k_phase_terms);
+    return rc;
+}
+
+static int launch_resid(pint_ctx* ctx, const EvalPlan& p) {
+    if (p.resid1 == RESID1_R12)
+        hipLaunchKernelGGL(k_resid12, dim3((ctx->nrblk + 3) / 4), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_ftay,
+                           ctx->d_rt, ctx->d_rp, ctx->d_rpart);
+    else if (p.resid1 == RESID1_64)
+        hipLaunchKernelGGL(k_resid1<64>, dim3((ctx->nrblk + 3) / 4), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_rp, ctx->d_rpart);
+    else if (p.resid1 == RESID1_256)
+        hipLaunchKernelGGL(k_resid1<RES_BT>, dim3(ctx->nrblk), dim3(RES_BT), 0, ctx->stream, ctx->d_psrs,
+                           ctx->d_inst, ctx->d_rblk_inst, ctx->nrblk, ctx->d_phhi, ctx->d_phlo, ctx->d_rp,
+                           ctx->d_rpart);
+    if (p.resid2 == RESID2_LAUNCH) launch_resid2(ctx, p.r2);
+    HIPCHK(hipGetLastError());
+    return PINT_OK;
+}
+
+// Evaluate phases/delays (+ design matrix) and residuals for every instance.
+int pint_eval(pint_ctx* ctx, int want_M) {
+    if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
+    hipSetDevice(ctx->device);
+    if (want_M < 0 || want_M > 2) return PINT_E_INVALID;
+    const EvalPlan p = plan_eval(ctx, want_M);
+    int rc;
+    if ((rc = launch_wait_copy(ctx, p))) return rc;  // (refused: nothing written)
+    commit_eval(ctx, p);
+    const EvalArgs a = eval_args(ctx, p);
+    record(ctx, want_M ? 2 : 0);
+    if ((rc = launch_source(ctx, p)) || (rc = launch_sw_geom(ctx, p, a)) || (rc = launch_eval_blocks(ctx, p, a)) ||
+        (rc = launch_post_passes(ctx, p, a)))
+        return rc;
+    record(ctx, want_M ? 3 : 1);
+    record(ctx, 4);
+    if ((rc = launch_resid(ctx, p))) return rc;
     record(ctx, 5);
     if (ctx->lazy) return PINT_OK;
-    int rc = check_status(ctx);
+    rc = check_status(ctx);
     update_timings(ctx);
     return rc;
 }
@@ -9966,7 +10127,7 @@ static int fit_step_impl(pint_ctx* ctx, int mode, const double* apply_lam, bool*
     // deferred reads of this slot's outputs enqueued since the last step_end go first (this
     // solve rewrites them)
     if (int rc = flush_cq_now(ctx)) return rc;
-    if (ctx->r2_pending && !can_defer_r2(ctx)) flush_r2(ctx);  // (a kernel below reads d_rt)
+    if (ctx->r2_pending && !can_defer_r2(ctx, ctx->m_compact)) flush_r2(ctx);  // (a kernel below reads d_rt)
     const bool sampled = ctx->timing_every <= 1 || (ctx->gram_calls % ctx->timing_every) == 0;
     const FitPlan p = plan_fit_step(ctx, mode, apply_lam != nullptr, sampled);
     ctx->plan = pint_plan_t{};
@@ -10131,31 +10292,29 @@ void pint_host_free(void* p) {
     hipHostFree(p);
 }
 
-int pint_apply_step(pint_ctx* ctx, const double* lambda_) {
-    if (!ctx || ctx->ninst <= 0 || !lambda_) return PINT_E_INVALID;
+// tables += lambda * step and the new tables' constants (k_apply): lambda_ per instance (host), or
+// null and lam_u for every instance
+static int apply_step(pint_ctx* ctx, const double* lambda_, double lam_u) {
     if (flush_restore(ctx)) return PINT_E_HIP;
     if (ctx->sigma_pending) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));  // k_sigma reads F0
-    HIPCHK(h2d(ctx->d_lam, lambda_, sizeof(double) * ctx->ninst, ctx->stream, false));
-    launch_apply(ctx, ctx->d_lam, 0.0);
+    if (lambda_) HIPCHK(h2d(ctx->d_lam, lambda_, sizeof(double) * ctx->ninst, ctx->stream, false));
+    launch_apply(ctx, lambda_ ? ctx->d_lam : nullptr, lam_u);
     HIPCHK(hipGetLastError());
-    ctx->ic_valid = true;
-    ctx->phases_valid = false;
+    tables_applied(ctx);
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
     return PINT_OK;
+}
+
+int pint_apply_step(pint_ctx* ctx, const double* lambda_) {
+    if (!ctx || ctx->ninst <= 0 || !lambda_) return PINT_E_INVALID;
+    return apply_step(ctx, lambda_, 0.0);
 }
 
 // The same step with one lambda for every instance (GLSFitter / WLSFitter take the full
 // step, fitter.py:2254-2263): a kernel argument, no host->device copy.
 int pint_apply_step_uniform(pint_ctx* ctx, double lambda_) {
     if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
-    if (flush_restore(ctx)) return PINT_E_HIP;
-    if (ctx->sigma_pending) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sigma, 0));  // k_sigma reads F0
-    launch_apply(ctx, nullptr, lambda_);
-    HIPCHK(hipGetLastError());
-    ctx->ic_valid = true;
-    ctx->phases_valid = false;
-    if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PINT_OK;
+    return apply_step(ctx, nullptr, lambda_);
 }
 
 // A fit step followed by tables += lambda * step (pint_fit_step + pint_apply_step_uniform):
@@ -10168,8 +10327,7 @@ int pint_fit_step_apply(pint_ctx* ctx, int mode, double lambda_) {
     bool applied = false;
     if (int rc = fit_step_impl(ctx, mode, &lambda_, &applied)) return rc;
     if (!applied) return pint_apply_step_uniform(ctx, lambda_);
-    ctx->ic_valid = true;
-    ctx->phases_valid = false;
+    tables_applied(ctx);
     return PINT_OK;
 }
 
@@ -10189,7 +10347,7 @@ int pint_save_tables(pint_ctx* ctx) {
                           ctx->stream));
     // the snapshot's per-instance constants, so a restore needs no k_prep (pint_eval)
     if (!ctx->d_ic0) HIPCHK(cmalloc((void**)&ctx->d_ic0, sizeof(InstConst) * ctx->ninst));
-    launch_prep(ctx, ctx->d_tables0, nullptr, ctx->d_ic0);
+    launch_prep(ctx, prep_lanes(ctx), ctx->d_tables0, nullptr, ctx->d_ic0);
     HIPCHK(hipGetLastError());
     ctx->ic0_valid = true;
     if (!ctx->lazy) HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -10409,6 +10567,8 @@ int pint_query(pint_ctx* ctx, int key) {
     if (key == PINT_QUERY_NREUSE) return ctx->n_batch_reuse;
     if (key == PINT_QUERY_NPLGLS) return ctx->n_plgls;
     if (key == PINT_QUERY_RESID_PATH) return ctx->resid_path;
+    if (key == PINT_QUERY_EVAL_PATH) return ctx->eval_path;
+    if (key == PINT_QUERY_EVAL_KINDS) return ctx->eval_kinds;
     ctx->err = "unknown query";
     return -PINT_E_INVALID;
 }

@@ -1191,6 +1191,20 @@ class Session:
         (PINT_QUERY_RESID_PATH); a reader that flushes the deferred second half adds its k_resid2 bit."""
         return int(self.L.pint_query(self.ctx, 7))
 
+    EVAL_PREP, EVAL_PREP_LANES, EVAL_PREP_RESTORE, EVAL_SNAPSHOT = 1, 2, 4, 8
+    EVAL_SW_GEOM, EVAL_SPIN, EVAL_MERGED, EVAL_MERGED_BUDGET, EVAL_KIND_BUDGET = 16, 32, 64, 128, 256
+
+    def eval_path(self):
+        """EVAL_* bits of what the last eval launched before its residual pass (PINT_QUERY_EVAL_PATH):
+        the source of the per-instance constants, k_sw_geom, the spin pass, the merged launch, and
+        whether the merged or some per-kind launch ran a build at a fixed register budget."""
+        return int(self.L.pint_query(self.ctx, 8))
+
+    def eval_kinds(self):
+        """Bit t set: block kind t (the binary model ids, then the FBn forms) got a launch of its own
+        in the last eval (PINT_QUERY_EVAL_KINDS)."""
+        return int(self.L.pint_query(self.ctx, 9))
+
     def last_plan(self):
         """The launch plan of the last fit_step (pint_last_plan) as a dict: the k_gram tile
         counts T launched (gram_T), the k_gram_v (key, vb) launches (gram_v), the general solve

@@ -2,7 +2,7 @@
 
 An RCase names the row counts of its pulsars (prefixes of one fake TOA set of N_ALL rows), the
 instances per pulsar, the session options and the flow; predict_mask repeats the dispatch
-arithmetic of pint_set_instances / pint_eval / launch_resid2 (pint_hip.hip) and returns the bit
+arithmetic of plan_batch / plan_eval / plan_resid2 (pint_hip.hip) and returns the bit
 mask Session.resid_path() must report, which every case also states by hand (`mask`).
 
 Shared with the GPU test so that the host checks (test_resid_cases.py) see the same inputs:

@@ -1427,14 +1427,20 @@ def test_single_model_batch_eval_matches_merged(monkeypatch):
         lays = [s.add(build_layout(m, t)) for m, t in items]
         s.set_instances([(l, pack_table(l, m)) for l, (m, _) in zip(lays, items)])
         s.eval(want_M=True)
+        paths = [(s.eval_path(), s.eval_kinds())]
         ev = [np.concatenate(x).copy() for x in s.read_eval()]
         M = [x.copy() for x in s.read_designmatrix()]
         s.eval(want_M=False)
+        paths.append((s.eval_path(), s.eval_kinds()))
         ev0 = [np.concatenate(x).copy() for x in s.read_eval()]
         s.close()
-        return ev, M, ev0
+        return ev, M, ev0, paths
 
     a, b = run(3), run(7)
+    # the two runs took the two paths: the isolated kind's own launch, the merged launch
+    for (pa, ka), (pb, kb) in zip(a[3], b[3]):
+        assert not pa & Session.EVAL_MERGED and ka == 1, (pa, ka)
+        assert pb & Session.EVAL_MERGED and kb == 0, (pb, kb)
     for x, y in zip(a[0] + a[2], b[0] + b[2]):
         np.testing.assert_array_equal(x, y)
     for x, y in zip(a[1], b[1]):
@@ -1485,14 +1491,19 @@ def test_isolated_eval_register_budgets_match(monkeypatch):
         lays = [s.add(build_layout(m, t)) for m, t in items]
         s.set_instances([(l, pack_table(l, m)) for l, (m, _) in zip(lays, items)])
         s.eval(want_M=True)
+        paths = [(s.eval_path() & Session.EVAL_KIND_BUDGET, s.eval_kinds())]
         ev = [np.concatenate(x).copy() for x in s.read_eval()]
         M = [x.copy() for x in s.read_designmatrix()]
         s.eval(want_M=False)
+        paths.append((s.eval_path() & Session.EVAL_KIND_BUDGET, s.eval_kinds()))
         ev0 = [np.concatenate(x).copy() for x in s.read_eval()]
         s.close()
-        return ev + M + ev0
+        return ev + M + ev0, paths
 
-    for x, y in zip(run(1), run(0)):
+    (a, pa), (b, pb) = run(1), run(0)
+    # the two runs took the two builds of the isolated kind's own launch, with M and without
+    assert pa == [(Session.EVAL_KIND_BUDGET, 1)] * 2 and pb == [(0, 1)] * 2, (pa, pb)
+    for x, y in zip(a, b):
         np.testing.assert_array_equal(x, y)
 
 
@@ -1510,12 +1521,16 @@ def test_large_one_model_batch_eval_budget_matches(monkeypatch):
         lay = s.add(build_layout(m0, t0))
         s.set_instances([(lay, pack_table(lay, m0))] * 14)
         s.eval(want_M=True)
+        path = (s.eval_path() & (Session.EVAL_KIND_BUDGET | Session.EVAL_MERGED), s.eval_kinds())
         ev = [np.concatenate(x).copy() for x in s.read_eval()]
         M = [x.copy() for x in s.read_designmatrix()]
         s.close()
-        return ev + M
+        return ev + M, path
 
-    for x, y in zip(run(3), run(0)):
+    (a, pa), (b, pb) = run(3), run(0)
+    # the ELL1 kind's own launch in both runs, at the budget in the first only
+    assert pa == (Session.EVAL_KIND_BUDGET, 1 << 1) and pb == (0, 1 << 1), (pa, pb)
+    for x, y in zip(a, b):
         np.testing.assert_array_equal(x, y)
 
 
