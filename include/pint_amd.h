@@ -474,7 +474,15 @@ int pint_chi2_wls(pint_ctx *ctx, double *chi2);
  * The quantisation block is eliminated by a Schur complement on the device (its normal
  * matrix block is diagonal), so it adds no Gram columns; on the compact layout each epoch
  * then couples to at most one DMX column (else the pulsar takes the full layout).  Call
- * before pint_set_instances. */
+ * before pint_set_instances.
+ * Overlapping epochs: a TOA listed in two epochs (two ECORR parameters whose masks share TOAs)
+ * is accepted here, but the block is then not diagonal and the per-epoch elimination is not
+ * that model.  Every entry point that rests on it refuses a batch holding such a pulsar with
+ * PINT_E_INVALID and a message naming overlapping ECORR epochs, before any launch and with no
+ * state changed (deferred work stays deferred, the plan of pint_last_plan is all-zero):
+ * pint_fit_step and pint_fit_step_apply in mode 1, pint_fit_step_enqueue, pint_chi2_gls,
+ * pint_noise_resids, and the likelihoods pint_noise_lnlike and pint_point_lnlike_gls.  The
+ * evaluation, mode 0 steps and the WLS chi2 are not affected. */
 int pint_set_ecorr(pint_ctx *ctx, int psr, int nep, const int32_t *ep_ptr, const int32_t *ep_idx,
                    const double *ep_phi);
 

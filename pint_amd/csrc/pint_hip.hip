@@ -9783,6 +9783,17 @@ static FitPlan plan_refused(const char* why) {
     return p;
 }
 
+// A TOA in two ECORR epochs (two ECORR parameters whose masks share TOAs): the epoch block of
+// the GLS normal matrix is then not diagonal, and the per-epoch elimination of k_ecorr /
+// k_gram<.., true> / k_wsolve (G - sum_e s_e s_e^T / D_e) and k_noise_ecorr's one coefficient
+// per TOA are not the model's.  The GLS step, its chi2 and its realisations refuse such a
+// batch, as the two likelihood entry points do.
+static bool batch_ecorr_overlap(const pint_ctx* ctx) {
+    for (int pi : ctx->upsr)
+        if (ctx->psrs[pi].dev.nep > 0 && ctx->psrs[pi].dev.ep_overlap) return true;
+    return false;
+}
+
 // The plan of pint_fit_step(mode) on the context's batch: the DMX-eliminated solve
 // (k_solve_dmx) for compact-layout instances when every such instance fits its LDS budget;
 // the others (and everything in the full layout) go to the blocked MFMA solve, or the
@@ -10122,6 +10133,11 @@ static int launch_solve(pint_ctx* ctx, const FitPlan& p) {
 // Gram + solve for every instance; apply_lam: also tables += *apply_lam * step when the solve
 // can carry it (*applied tells), pint_fit_step_apply.
 static int fit_step_impl(pint_ctx* ctx, int mode, const double* apply_lam, bool* applied) {
+    if (mode == 1 && batch_ecorr_overlap(ctx)) {  // (before the deferred work below: nothing enqueued)
+        ctx->plan = pint_plan_t{};
+        ctx->err = "pint_fit_step: overlapping ECORR epochs (a TOA in two epochs)";
+        return PINT_E_INVALID;
+    }
     if (flush_restore(ctx)) return PINT_E_HIP;
     hipSetDevice(ctx->device);
     // deferred reads of this slot's outputs enqueued since the last step_end go first (this
@@ -10380,6 +10396,10 @@ static int flush_restore(pint_ctx* ctx) {
 // Woodbury GLS chi2 of the current residuals; requires a previous pint_fit_step(mode=1)
 // (Sigma factor) and the red-noise columns of the last design matrix.
 int pint_chi2_gls(pint_ctx* ctx, double* chi2) {
+    if (ctx && batch_ecorr_overlap(ctx)) {  // k_wsolve corrects per epoch (no Sigma factor of such a batch exists)
+        ctx->err = "pint_chi2_gls: overlapping ECORR epochs (a TOA in two epochs)";
+        return PINT_E_INVALID;
+    }
     flush_r2(ctx);
     if (flush_chi2(ctx)) return PINT_E_HIP;
     int R = 0;
@@ -10652,6 +10672,10 @@ int pint_fit_step_enqueue(pint_ctx* ctx, int restore, int mode, double lambda_, 
     if (!ctx || ctx->ninst <= 0 || !slot) return PINT_E_INVALID;
     if (!ctx->lazy || ctx->capturing) { ctx->err = "pint_fit_step_enqueue needs lazy mode (no capture)"; return PINT_E_INVALID; }
     if (mode != 1) { ctx->err = "pint_fit_step_enqueue: GLS steps (mode 1) only"; return PINT_E_INVALID; }
+    if (batch_ecorr_overlap(ctx)) {  // (before the restore and the evaluation)
+        ctx->err = "pint_fit_step_enqueue: overlapping ECORR epochs (a TOA in two epochs)";
+        return PINT_E_INVALID;
+    }
     int rc = PINT_OK;
     // PINT_TRACE_ENQ=1: the host time of each enqueue stage (a stall > 1 ms is printed)
     static const bool tr = getenv("PINT_TRACE_ENQ") && atoi(getenv("PINT_TRACE_ENQ"));
@@ -10792,6 +10816,10 @@ int pint_inst_status(pint_ctx* ctx, int32_t* out) {
 // pint_check / pint_check_step; the next solve waits for them (copy_pending).
 int pint_noise_resids(pint_ctx* ctx, double* red, double* ecorr) {
     if (!ctx || ctx->ninst <= 0) return PINT_E_INVALID;
+    if (batch_ecorr_overlap(ctx)) {  // (no GLS step of such a batch exists to realise)
+        ctx->err = "pint_noise_resids: overlapping ECORR epochs (a TOA in two epochs)";
+        return PINT_E_INVALID;
+    }
     hipSetDevice(ctx->device);
     const long need = 3 * std::max<long>(1, ctx->tot_out);  // red, ECORR, DM noise
     if (need > ctx->noise_cap) {

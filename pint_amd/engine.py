@@ -65,6 +65,13 @@ class PulsarLayout:
     # Wave's (a, b) pairs in the table: (slot, parameter name), two plain doubles at the slot
     pairs: list = field(default_factory=list)
 
+    @property
+    def ep_overlap(self) -> bool:
+        """A TOA lies in two ECORR epochs (two ECORR parameters whose masks share TOAs).  The
+        device's GLS step, GLS chi2, realisations and ECORR likelihoods eliminate one diagonal
+        block per epoch and refuse such a pulsar (PINT_E_INVALID, "overlapping ECORR epochs")."""
+        return bool(self.nep) and len(np.unique(self.ep_idx)) != len(self.ep_idx)
+
 
 def _track_mode(model, toas, track_mode):
     """residuals.py:133-149 auto-selection."""

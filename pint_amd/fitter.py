@@ -143,6 +143,17 @@ class BatchFit:
         self.grid_like = grid is not None or (isinstance(tables, np.ndarray) and tables.ndim == 2 and len(layouts) > 0
                                               and len(set(map(id, layouts))) == 1)  # one layout object (C-level scan)
         self.layouts0 = layouts if grid is not None else list(layouts)  # (a grid's list is its own)
+        if self.gls:
+            # two ECORR parameters whose masks share TOAs: the device eliminates one diagonal block
+            # per epoch, which is not that model (pint_fit_step refuses it); say so before any step
+            for lay in (layouts[:1] if self.grid_like else layouts):
+                if lay.ep_overlap:
+                    if self.own_session:
+                        self.s.close()
+                    raise NotImplementedError(
+                        f"GLS fits on the device do not take overlapping ECORR epochs: a TOA of "
+                        f"{getattr(lay.model, 'name', '') or 'a pulsar'} lies in two epochs (ECORR parameters "
+                        f"{', '.join(sorted(set(lay.ep_param)))} select common TOAs)")
         self._bind(list(layouts), tables)
         # wideband (WidebandTOAFitter / WidebandDownhillFitter): the DM rows join every fit
         # step (k_wb_gram) and every chi2 (the DM chi2 of WidebandTOAResiduals)

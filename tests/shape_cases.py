@@ -15,6 +15,12 @@ fields set: free DM Taylor terms, DMJUMPs and NE_SW beside the ntim timing colum
 frozen DMX bins and DMJUMPs, a bin of one TOA, the TOA order; bin_rows / free_rows map TOAs to
 the model's bins and to the compact DMX columns, and predict_plan adds k_dmx, k_ecorr_dmx and
 k_wb_gram to the plan.  Cases without those fields predict what they did before.
+
+The ECORR sweep (ecorr_cases.py, test_ecorr_sweep.py) adds its own: the ECORR lines of the par
+(ecorr_par), a pulsar the ECORR rule of pint_set_ecorr takes off the compact layout (ecorr_off),
+a PhaseOffset with PHOFF frozen (phoff: no Offset column), PLDMNoise modes among the nred
+Fourier modes (ndmn) and one DMX bin edge moved to a chosen MJD (dmx_edge); predict_plan takes
+ECORR onto the small path (k_gram_s and the ECORR rows by k_gram<1, 128, true>).
 """
 from dataclasses import dataclass, replace
 
@@ -68,6 +74,12 @@ class Case:
     order: str = ""          # TOA order: "" (by time), "reverse", "shuffle"
     one_toa: bool = False    # bin 2 shrunk onto one TOA (its other TOAs lie in no bin)
     nesw: bool = False       # NE_SW free
+    # ECORR cases (ecorr_cases.py; test_ecorr_sweep.py)
+    ecorr_par: tuple = ()    # ((flag, value, ECORR in us), ...) instead of the one "ECORR -f fake 0.5"
+    ecorr_off: bool = False  # pint_set_ecorr takes the pulsar off the compact layout (an epoch in two free bins, a TOA in two epochs)
+    phoff: bool = False      # PhaseOffset with PHOFF frozen: no Offset column (ntim free parameters), the virtual ones row
+    ndmn: int = 0            # ... of the nred Fourier modes, the last ndmn are PLDMNoise's
+    dmx_edge: tuple = ()     # (a, mjd): the edge between bins a and a + 1 (0-based) moved to mjd
 
     @property
     def ndmx_free(self):
@@ -115,11 +127,22 @@ def wavex_freqs(nwx, nred=0):
 
 def par_of(c: Case) -> str:
     from pint_amd.simulation import pta_par
-    par = pta_par(SEED, "", ndmx=c.ndmx, nmodes=max(c.nred, 1))
-    if c.nred == 0:
+    par = pta_par(SEED, "", ndmx=c.ndmx, nmodes=max(c.nred - c.ndmn, 1))
+    if c.nred - c.ndmn == 0:
         par = "\n".join(l for l in par.split("\n") if not l.startswith("TNRed")) + "\n"
-    if c.ecorr:
+    if c.ecorr_par:
+        par += "".join(f"ECORR {k} {v} {x!r}\n" for k, v, x in c.ecorr_par)
+    elif c.ecorr:
         par += "ECORR -f fake 0.5\n"
+    if c.phoff:
+        par += "PHOFF 0.05\n"
+    if c.ndmn:
+        par += f"TNDMAMP -13.2\nTNDMGAM 2.8\nTNDMC {c.ndmn}\n"
+    if c.dmx_edge:
+        a, x = c.dmx_edge
+        sub = {f"DMXR2_{a + 1:04d}": x, f"DMXR1_{a + 2:04d}": x}
+        par = "\n".join(f"{l.split()[0]} {sub[l.split()[0]]!r}" if l.split() and l.split()[0] in sub else l
+                        for l in par.split("\n"))
     if c.wb:
         par = wideband_par(c, par)
     return par
@@ -161,7 +184,7 @@ def model_of(c: Case):
     from pint_amd.timing_model import get_model
     from pint_amd.wavex import wavex_setup
     m = get_model(par_of(c))
-    nb, nwx = timing_split(c.ntim)
+    nb, nwx = timing_split(c.ntim + int(c.phoff))
     free = list(TIMING[:nb])
     if nwx:
         wavex_setup(m, TSPAN, freqs=wavex_freqs(nwx, c.nred))
@@ -195,6 +218,9 @@ def dmx_ranges(c):
         dt = TSPAN / (n - 1)
         k = int(np.ceil((rng[2][0] - MJD0) / dt))
         rng[2] = (round(MJD0 + (k - 0.4) * dt, 5), round(MJD0 + (k + 0.4) * dt, 5))
+    if c.dmx_edge:
+        a, x = c.dmx_edge
+        rng[a], rng[a + 1] = (rng[a][0], float(x)), (float(x), rng[a + 1][1])
     return rng
 
 
@@ -211,7 +237,7 @@ def bin_rows(c, mjd):
 
 def free_rows(c, mjd):
     """The compact DMX column (index among the free bins) of every TOA, -1 without one."""
-    if not (c.dmx_frozen or c.one_toa):
+    if not (c.dmx_frozen or c.one_toa or c.dmx_edge):
         return dmx_rows(mjd, c.ndmx)
     free = [a for a in range(c.ndmx) if a not in c.dmx_frozen]
     col = np.full(c.ndmx + 1, -1)
@@ -287,8 +313,8 @@ def vgram_layout(c: Case, n, drow, nsplit):
 
 
 def predict_plan(c: Case, n, mjd):
-    """The plan of pint_fit_step(c.mode) for a batch of this one pulsar (ECORR off the small
-    path; wideband DM rows with c.wb; default options but those the case names), in
+    """The plan of pint_fit_step(c.mode) for a batch of this one pulsar (wideband DM rows with
+    c.wb; default options but those the case names), in
     Session.last_plan()'s form.  mjd: the TOAs' MJDs in the order they are uploaded."""
     plan = dict(gram_T=(), gram_v=(), solve="none", gram_ecorr=False, gram_s=False, greduce=False, dmx_rows=False,
                 dmx=False, ecorr_dmx=False, wb_gram=False, fuse_sigma=False, side_sigma=False, do_sigma=False,
@@ -297,7 +323,7 @@ def predict_plan(c: Case, n, mjd):
         return plan
     K, Kp = c.K, _pad16(c.K + 1)
     cmp = c.layout == "fit"
-    dsplit = c.ndmx_free >= 8
+    dsplit = c.ndmx_free >= 8 and not c.ecorr_off  # (pint_set_ecorr: the Schur rows would couple DMX columns)
     Kd = c.ndense + 2 * c.nred
     Kpd = _pad16(Kd + 1)
     nsplit = min(c.nsplit, max(1, (n + 63) // 64))
@@ -320,8 +346,8 @@ def predict_plan(c: Case, n, mjd):
         # rows of a bin that are not contiguous: k_dmx gathers them (k_dmx_rows returns at once)
         plan["dmx"] = bool(cmp and dsplit and not rows_contiguous(drow, c.ndmx_free))
     nep = bool(c.ecorr and c.mode == 1)  # the ECORR Schur partial: k_gram<T, ch, true> and one more part
-    if c.ecorr and plan["gram_s"]:
-        raise NotImplementedError("ECORR cases: off the small path")
+    if nep and plan["gram_s"]:
+        plan["gram_T"] = (1,)  # small instances: k_gram_s, their ECORR rows by k_gram<1, 128, true>
     plan["gram_ecorr"] = nep
     # compact layout with ECORR (every epoch within one DMX column): its share of the DMX rows
     plan["ecorr_dmx"] = bool(nep and plan["dmx_rows"])

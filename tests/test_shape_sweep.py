@@ -153,7 +153,7 @@ import numpy as np
 import pytest
 
 import shape_cases as SC
-from ld_util import LD, host_fourier, ld_gram, ld_inverse, ld_solve, ld_woodbury_chi2
+from ld_util import LD, chol64, host_fourier, ld_gram, ld_woodbury_chi2, step_errors  # noqa: F401  (chol64: test_wideband_sweep.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -215,12 +215,6 @@ def reference(c, toas):
     return _REF[key]
 
 
-def chol64(A, B):
-    """float64 LAPACK Cholesky solve A X = B."""
-    L = np.linalg.cholesky(np.asarray(A, dtype=np.float64))
-    return np.linalg.solve(L.T, np.linalg.solve(L, np.asarray(B, dtype=np.float64)))
-
-
 @pytest.mark.parametrize("c", CASES, ids=[c.name for c in CASES])
 def test_shape(c, toa_sets, monkeypatch):
     from pint_amd import _lib
@@ -275,25 +269,7 @@ def test_shape(c, toa_sets, monkeypatch):
     eg = float(np.max(np.abs(G - Gref) / np.outer(D, D)))
     ec = float(np.max(np.abs(colsq / csref - 1)))
     # (c) step, errors, covariance: the device's own normalised system
-    Kf = ncol if c.mode == 0 else K
-    norm = np.sqrt(np.diag(G)[:Kf]) if c.mode == 0 else np.sqrt(colsq)
-    inv = 1.0 / norm
-    Ad = G[:Kf, :Kf] * (inv[:, None] * inv[None, :])
-    if c.mode == 1 and c.nred:
-        i = np.arange(ncol, K)
-        Ad[i, i] += (inv[ncol:] * inv[ncol:]) / np.asarray(lay.red_phi)
-    bd = G[:Kf, K] * inv
-    x = ld_solve(Ad, bd) * inv
-    X = ld_inverse(Ad) * np.outer(inv, inv)
-    sg = np.sqrt(np.diag(X))
-    X64 = chol64(Ad, np.eye(Kf)) * np.outer(inv, inv)
-    e_ref = float(np.max(np.abs(chol64(Ad, bd) * inv - x) / sg))
-    e_dev = float(np.max(np.abs(dp[:Kf] - x) / sg))
-    s_ref = float(np.max(np.abs(np.sqrt(np.diag(X64)) / sg - 1)))
-    s_dev = float(np.max(np.abs(er[:Kf] / sg - 1)))
-    ss = np.outer(sg[:ncol], sg[:ncol])
-    c_ref = float(np.max(np.abs(X64[:ncol, :ncol] - X[:ncol, :ncol]) / ss))
-    c_dev = float(np.max(np.abs(cov - X[:ncol, :ncol]) / ss))
+    e_dev, e_ref, s_dev, s_ref, c_dev, c_ref = step_errors(G, colsq, K, ncol, c.mode, lay.red_phi, dp, er, cov)
     line = (f"{c.name}: K {K} n {toas.ntoas} gram {eg:.1e} colsq {ec:.1e} step {e_dev:.1e} (ref {e_ref:.1e}) "
             f"errs {s_dev:.1e} (ref {s_ref:.1e}) cov {c_dev:.1e} (ref {c_ref:.1e})")
     # (d) GLS chi2
